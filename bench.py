@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Mkeys/s of the whole LSD radix sort and scatter-pass HBM roofline fraction.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 One "step" = one complete sort of the resident input (all 8 passes for uint32: per pass
 histogram -> scan -> paste -> reorder).  At N=1 the workload is BASELINE.json configs[1]:
@@ -27,6 +27,12 @@ timed single-threaded on a bounded sample on this host (rank 0).  At N=1 the sam
 whole workload and the array it sorted is then compared, key for key, with the GPU's
 output (`config.verified`).  At N>1 the ranks' outputs are gathered on rank 0 and compared
 with a host sort of all the inputs.
+
+--dump-outputs DIR writes what the last timed step computed, the sorted keys (and the payload with --payload) as a
+caller receives them, to DIR/<name>.npy in float64: every value exact (8-byte keys as two arrays of their high and low
+32 bits), at most DUMP_BUDGET values in all, so a larger output is a fixed, seeded sample of positions.  At N>1 every rank
+writes its own shard's arrays, prefixed rank<r>_.  The inputs depend on the arguments alone, so two builds can be compared
+array for array.
 
 RSX_BENCH_REHEARSAL=1 (tests only) swaps the device side for the CPU test double of
 tests/_bench_rehearsal.py under gloo, so that the launcher and every line of the N>1 rank
@@ -54,6 +60,8 @@ KIND_CODES = {"Zeros": 0, "Range": 1, "InvertedRange": 2, "Random": 3, "RandomDi
 DTYPE_CODES = {"uint32": 0, "int32": 1, "uint64": 2, "int64": 3}
 METRIC = "Mkeys/s + scatter-pass HBM GB/s (% of peak), 2^28 uint32 keys"
 BASE_SEED = 0x5EEDCAFEF00D
+DUMP_BUDGET = 1 << 22          # float64 values over all --dump-outputs arrays of all ranks: 32 MiB
+DUMP_SEED = 0xD0E5EED
 
 
 def make_input(kind: str, dtype: str, n: int, seed: int) -> np.ndarray:
@@ -136,6 +144,28 @@ def load_traffic(workload: str):
     return entry.get("reorder_hbm_bytes_per_launch"), f"replayed from profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes on kernel sources {now})"
 
 
+def dump_outputs(out_dir: str, rank: int, world: int, keys: np.ndarray, payload: np.ndarray | None) -> list[str]:
+    """Write this rank's sorted keys (and payload) to out_dir as exact float64 .npy files; returns the names written.  An
+    array longer than its share of DUMP_BUDGET is sampled at the same seeded positions for the same length."""
+    arrays = {}
+    if keys.dtype.itemsize == 8:
+        bits = keys.view(np.uint64)
+        arrays["keys_hi32"], arrays["keys_lo32"] = bits >> np.uint64(32), bits & np.uint64(0xFFFFFFFF)
+    else:
+        arrays["keys"] = keys
+    if payload is not None:
+        arrays["payload"] = payload.view(np.uint32)
+    share = DUMP_BUDGET // (len(arrays) * world)
+    idx = None
+    if keys.size > share:
+        idx = np.sort(np.random.default_rng([DUMP_SEED, rank]).integers(0, keys.size, share))
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), (arr if idx is None else arr[idx]).astype(np.float64))
+    return [prefix + name for name in arrays]
+
+
 def free_port() -> int:
     import socket
     with socket.socket() as sock:
@@ -188,7 +218,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-verify-full", action="store_true", help="N>1: skip the gather of all outputs on rank 0 and keep only the checksum / boundary checks")
     ap.add_argument("--no-events", action="store_true", help="no HIP events inside the timed region (roofline then comes from the instrumented steps after it)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float64, a seeded sample of large outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main() -> None:
@@ -324,6 +358,19 @@ def main() -> None:
     rt = eng.timings(reset=True)
     if hasattr(eng, "sync"):
         eng.sync()              # also reports a fused table scan that timed out in the last step (earlier ones: the sorter's check)
+    dumped = None
+    if args.dump_outputs:
+        # the last timed step's result, before the instrumented steps below sort again
+        if sharded and sorter.result_in_out:
+            sync()
+            out_keys = obuf[:n_local].cpu().numpy().view(np.dtype(args.dtype))
+            out_pay = opay[:n_local].cpu().numpy() if args.payload else None
+        elif args.payload:
+            out_keys, out_pay = eng.download(want_perm=True)
+        else:
+            out_keys, out_pay = eng.download(), None
+        dumped = dump_outputs(args.dump_outputs, rank, world, out_keys, out_pay)
+        del out_keys, out_pay
     eng.set_option(rsx.OPT_PROFILE, 1)
     sorter.record_timeline = sharded and not rehearsal
     for _ in range(2):
@@ -475,6 +522,8 @@ def main() -> None:
         line["config"]["note"] = "8-bit digits: a separately reported variant; BASELINE's configuration is 4-bit digits"
     if base_entry is not None:
         line["cpu_baseline"] = base_entry
+    if dumped is not None:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}       # rank 0's; rank r writes rank<r>_*
     if rehearsal:
         line["metric"] = "REHEARSAL on a CPU test double (tests only) — not a measurement; " + METRIC
         line["value"] = None

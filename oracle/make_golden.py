@@ -17,7 +17,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from _oracle import Oracle, RefOracle, build_oracle  # noqa: E402
+from _oracle import (REFERENCE_MATRIX_KINDS, REFERENCE_MATRIX_SIZES, Oracle, RefOracle, build_oracle,  # noqa: E402
+                     outside_oracle_domain, reference_fuzz_cases)
 
 DT = ["uint32", "int32", "uint64", "int64"]
 KINDS = ["Zeros", "Range", "InvertedRange", "Random"]
@@ -55,6 +56,8 @@ def main() -> None:
         "random_first8": {},
         "known_answers": [],
         "small_vectors": [],
+        "reference_matrix": [],
+        "reference_fuzz": [],
     }
     for dt in DT:
         out["random_first8"][dt] = [int(v) for v in ref.dataset("Random", dt, 8)]
@@ -73,6 +76,20 @@ def main() -> None:
             "dtype": dt, "kind": "Random", "n": 64,
             "input": [int(v) for v in src], "sorted": [int(v) for v in ref.radix_sort(src)],
         })
+    # the reference's answers to the matrix and the fuzzed inputs of test_oracle.py (sorted_digest null: outside the domain)
+    for dt in DT:
+        for kind in REFERENCE_MATRIX_KINDS:
+            for n in REFERENCE_MATRIX_SIZES:
+                src = ref.dataset(kind, dt, n)
+                out["reference_matrix"].append({
+                    "dtype": dt, "kind": kind, "n": n, "input_digest": dig(src),
+                    "sorted_digest": None if outside_oracle_domain(src) else dig(ref.radix_sort(src)),
+                })
+        for lo, hi, src in reference_fuzz_cases(dt):
+            out["reference_fuzz"].append({
+                "dtype": dt, "lo": lo, "hi": hi, "n": int(src.size),
+                "input_digest": dig(src), "sorted_digest": dig(ref.radix_sort(src)),
+            })
     for dt, vals in KNOWN_ANSWER_INPUTS:
         src = np.array(vals, dtype=dt)
         out["known_answers"].append({"dtype": dt, "input": vals, "output": [int(v) for v in ref.radix_sort(src)]})

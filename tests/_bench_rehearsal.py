@@ -20,8 +20,8 @@ class RehearsalEngine(_CpuEngineDouble):
         zero = SimpleNamespace(min_ms=0.0, max_ms=0.0, avg_ms=0.0, sum_ms=0.0, n=0)
         return SimpleNamespace(histogram=zero, scan=zero, paste=zero, reorder=zero, total=zero)
 
-    def download(self):
-        return self.result
+    def download(self, want_perm=False):
+        return (self.result, self.result_payload) if want_perm else self.result
 
     def close(self):
         pass

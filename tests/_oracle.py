@@ -26,6 +26,31 @@ def _code(dtype) -> int:
     return DTYPES[np.dtype(dtype).name]
 
 
+# The restatement-vs-reference comparisons of tests/test_oracle.py.  oracle/make_golden.py stores the reference's answers to
+# exactly these inputs in tests/golden/oracle_golden.json, so the comparison runs wherever the suite does.
+REFERENCE_MATRIX_KINDS = ("Zeros", "Range", "InvertedRange", "Random")
+REFERENCE_MATRIX_SIZES = (1, 2, 7, 1000, 1024, 4096, 65536)
+
+
+def outside_oracle_domain(keys: np.ndarray) -> bool:
+    """Raw maximum == numeric_limits::min() of a signed type: the reference negates it in the signed type (for int32 through
+    C's abs(int), which wins overload resolution over CRadixSortCPU.h:20-25) — undefined behaviour that ends in a division by
+    zero.  No answer exists to compare with."""
+    return np.dtype(keys.dtype).kind == "i" and keys.size > 0 and int(keys.max()) == np.iinfo(keys.dtype).min
+
+
+def reference_fuzz_cases(dtype):
+    """60 seeded random inputs per key type, (lo, hi, keys) each: a mix of magnitudes, so that the reference's short round
+    counts are hit too."""
+    rng = np.random.default_rng(1234)
+    info = np.iinfo(dtype)
+    for trial in range(60):
+        n = int(rng.integers(1, 3000))
+        hi = [7, 8, 63, 64, 511, 4096, 2**20, int(info.max)][trial % 8]
+        lo = 0 if info.min == 0 or trial % 3 else max(int(info.min), -hi)
+        yield lo, hi, rng.integers(lo, hi, size=n, dtype=dtype, endpoint=True)
+
+
 def build_oracle(ref: bool = True) -> None:
     """Compile oracle/liboracle.so (and oracle/_ref when the reference tree exists)."""
     subprocess.run(["make", "-C", ORACLE_DIR, "liboracle.so"], check=True, capture_output=True)

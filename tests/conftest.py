@@ -32,10 +32,10 @@ def oracle():
 
 @pytest.fixture(scope="session")
 def ref_oracle():
+    """The reference's own headers (oracle/_ref) where they were built, else None: the tests then check the reference's
+    answers stored in tests/golden/ alone."""
     from _oracle import RefOracle
-    if not RefOracle.available():
-        pytest.skip("oracle/_ref not built (needs /root/reference at build time)")
-    return RefOracle()
+    return RefOracle() if RefOracle.available() else None
 
 
 @pytest.fixture(scope="session")

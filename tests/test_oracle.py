@@ -3,12 +3,15 @@
 Pins, in order of authority:
  1. tests/golden/oracle_golden.json — produced by the reference's own headers
     (oracle/make_golden.py via oracle/_ref); checked everywhere, including the GPU box.
- 2. oracle/_ref itself, when present: restatement == reference byte-for-byte on a
-    matrix of inputs and on fuzzed inputs.
+ 2. The reference's answers on a matrix of inputs and on fuzzed inputs, stored in
+    the same file: restatement == reference byte-for-byte (and against oracle/_ref
+    itself, live, where it is built).
  3. Sample values the survey recorded from the reference headers.
 """
 import numpy as np
 import pytest
+
+from _oracle import REFERENCE_MATRIX_KINDS, REFERENCE_MATRIX_SIZES, outside_oracle_domain, reference_fuzz_cases
 
 DT = ["uint32", "int32", "uint64", "int64"]
 KINDS = ["Zeros", "Range", "InvertedRange", "Random"]
@@ -53,32 +56,37 @@ def test_survey_recorded_samples(oracle, golden):
 
 
 @pytest.mark.parametrize("dt", DT)
-def test_restatement_equals_reference_matrix(oracle, ref_oracle, dt):
-    for kind in KINDS:
-        for n in (1, 2, 7, 1000, 1024, 4096, 65536):
+def test_restatement_equals_reference_matrix(oracle, golden, ref_oracle, dt):
+    # The reference's answers as oracle/make_golden.py stored them; the live reference too where oracle/_ref is built.
+    rows = {(r["kind"], r["n"]): r for r in golden["reference_matrix"] if r["dtype"] == dt}
+    assert len(rows) == len(REFERENCE_MATRIX_KINDS) * len(REFERENCE_MATRIX_SIZES)
+    for kind in REFERENCE_MATRIX_KINDS:
+        for n in REFERENCE_MATRIX_SIZES:
+            row = rows[(kind, n)]
             a = oracle.dataset(kind, dt, n)
-            b = ref_oracle.dataset(kind, dt, n)
-            assert np.array_equal(a, b), (kind, n)
-            if np.dtype(dt).kind == "i" and int(a.max()) == np.iinfo(dt).min:
-                # Raw maximum == numeric_limits::min(): the reference negates it in the
-                # signed type (for int32 through C's abs(int), which wins overload
-                # resolution over CRadixSortCPU.h:20-25) — undefined behaviour that
-                # ends in a division by zero here.  Outside the oracle's domain.
+            assert oracle.digest(a) == row["input_digest"], row
+            if ref_oracle is not None:
+                assert np.array_equal(a, ref_oracle.dataset(kind, dt, n)), (kind, n)
+            if outside_oracle_domain(a):
+                assert row["sorted_digest"] is None, row
                 continue
-            assert np.array_equal(oracle.radix_sort(a), ref_oracle.radix_sort(b)), (kind, n)
+            got = oracle.radix_sort(a)
+            assert oracle.digest(got) == row["sorted_digest"], row
+            if ref_oracle is not None:
+                assert np.array_equal(got, ref_oracle.radix_sort(a)), (kind, n)
 
 
 @pytest.mark.parametrize("dt", DT)
-def test_restatement_equals_reference_fuzz(oracle, ref_oracle, dt):
-    rng = np.random.default_rng(1234)
-    info = np.iinfo(dt)
-    for trial in range(60):
-        n = int(rng.integers(1, 3000))
-        # mix of magnitudes so short round counts (the reference's defect) are hit too
-        hi = [7, 8, 63, 64, 511, 4096, 2**20, int(info.max)][trial % 8]
-        lo = 0 if info.min == 0 or trial % 3 else max(int(info.min), -hi)
-        x = rng.integers(lo, hi, size=n, dtype=dt, endpoint=True)
-        assert np.array_equal(oracle.radix_sort(x), ref_oracle.radix_sort(x)), (trial, n, lo, hi)
+def test_restatement_equals_reference_fuzz(oracle, golden, ref_oracle, dt):
+    rows = [r for r in golden["reference_fuzz"] if r["dtype"] == dt]
+    cases = list(reference_fuzz_cases(dt))
+    assert len(rows) == len(cases)
+    for trial, (row, (lo, hi, x)) in enumerate(zip(rows, cases)):
+        assert (row["lo"], row["hi"], row["n"], row["input_digest"]) == (lo, hi, x.size, oracle.digest(x)), (trial, row)
+        got = oracle.radix_sort(x)
+        assert oracle.digest(got) == row["sorted_digest"], (trial, row)
+        if ref_oracle is not None:
+            assert np.array_equal(got, ref_oracle.radix_sort(x)), (trial, x.size, lo, hi)
         assert oracle.round_count(x) >= 0
 
 
