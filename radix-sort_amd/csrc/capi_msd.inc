@@ -167,11 +167,14 @@ int rsx_msd_plan_wait(rsx_engine* e, uint64_t* wave_start, uint64_t* wave_count,
 int rsx_msd_push(rsx_engine* e, int wave, const void* d_staging, const uint32_t* d_staging_payload, const uint64_t* d_peer_keys, const uint64_t* d_peer_payload, int parts,
                  void* hip_stream)
 {
-    if (!e || !d_staging || !d_peer_keys) return fail(RSX_CALCULATION_FAILED, "rsx_msd_push: null argument");
+    if (!e || !d_peer_keys) return fail(RSX_CALCULATION_FAILED, "rsx_msd_push: null argument");
     if (!e->msd_planned) return fail(RSX_CALCULATION_FAILED, "rsx_msd_push: must follow rsx_msd_plan");
     const int waves = (1 << e->msd_bits) / e->msd_world;
     if (wave < 0 || wave >= waves) return fail(RSX_CALCULATION_FAILED, "rsx_msd_push: wave out of range");
-    if (e->has_payload && (!d_staging_payload || !d_peer_payload)) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_msd_push: payload engine needs payload buffers");
+    // an empty shard has an empty staging buffer (often no address at all): its segments are all empty, the kernel never reads it
+    const bool has_keys = e->msd_n > 0;
+    if (has_keys && !d_staging) return fail(RSX_CALCULATION_FAILED, "rsx_msd_push: null staging buffer");
+    if (e->has_payload && (!d_peer_payload || (has_keys && !d_staging_payload))) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_msd_push: payload engine needs payload buffers");
     if (bind_device(e, RSX_CALCULATION_FAILED) != RSX_OK) return RSX_CALCULATION_FAILED;
     if (parts <= 0) parts = std::max(16, 128 / e->msd_world);       // at least 128 workgroups per wave: enough loads in flight for a link- (or, on one GPU, HBM-) bound copy
     if (parts > 256) parts = 256;

@@ -52,7 +52,7 @@ production); tests inject a CPU test double through the same methods so the spli
 from __future__ import annotations
 
 from .planner import (GROUP_DOUBLING, GROUP_SINGLE, MAX_SPLITTERS, PEER_ENABLE_THEN_POINTER, PEER_OPEN_IPC, CapacityError, ExchangePlan,  # noqa: F401  (re-exported)
-                      balanced_owner, check_capacity, choose_splitters, group_pass_units, peer_access, plan_from_table, range_buckets, split_cuts, split_plan,
+                      balanced_owner, check_capacity, check_capacity_extent, choose_splitters, group_pass_units, peer_access, plan_from_table, range_buckets, split_cuts, split_plan,
                       wave_extents, wave_groups, wave_layout)
 
 RADIX = 16                  # buckets of the one-shot paths (top / split / range): the 16-bucket partition kernels
@@ -62,6 +62,9 @@ ROW_CAPS = MSD_SLOTS        # [ROW_CAPS], [ROW_CAPS + 1]: this rank's receive / 
 ROW_STATUS = MSD_SLOTS + 2  # non-zero: this rank's engine reported an error of an earlier step
 ROW_LEN = MSD_SLOTS + 3
 SAMPLES_PER_RANK = 1024
+# the buffers the C ABI reads 16 bytes per lane and refuses (on the host) when they are not 16-byte aligned; bit i + 1 of a status word
+# says that this rank's buffer ALIGNED_BUFFERS[i] is not (bit 0: the engine reported an error of an earlier step)
+ALIGNED_BUFFERS = ("keys", "payload", "staging", "recv", "recv_payload")
 
 
 class EngineStatusError(RuntimeError):
@@ -97,8 +100,17 @@ def recv_splits(all_send_splits: list[list[int]], rank: int) -> list[int]:
     return [row[rank] for row in all_send_splits]
 
 
+class MisalignedBufferError(ValueError):
+    """Some rank passed a buffer the engine reads 16 bytes per lane at an address that is not 16-byte aligned (a view at an odd
+    offset, say).  Found before the first collective and carried in the status word: EVERY rank raises it in the same step."""
+
+
 def _raise_together(statuses: list[int]) -> None:
-    bad = [r for r, s in enumerate(statuses) if s]
+    misaligned = [f"rank {r} {name}" for r, s in enumerate(statuses) for i, name in enumerate(ALIGNED_BUFFERS) if (int(s) >> (i + 1)) & 1]
+    if misaligned:
+        raise MisalignedBufferError(f"buffers that are not 16-byte aligned: {', '.join(misaligned)} (the engine reads them 16 bytes per lane); "
+                                    "every rank stops here together")
+    bad = [r for r, s in enumerate(statuses) if int(s) & 1]
     if bad:
         raise EngineStatusError(f"rank(s) {bad} reported an engine error of an earlier step (a fused table scan that timed out: that step's result is "
                                 "undefined); every rank stops here together")
@@ -340,12 +352,25 @@ class ShardedSorter:
             self._status_text = str(exc)
             return 1
 
+    def _misaligned(self, keys, payload, staging, recv, recv_payload) -> int:
+        """Status bits (ALIGNED_BUFFERS) of the buffers this step would hand to the engine at an address that is not 16-byte aligned:
+        the shard, its payload and the staging buffer when the shard has keys; the receive buffers (inputs of the local sort) unless the
+        peer-store exchange receives into its own."""
+        has_keys, receives = keys.numel() > 0, self.strategy != "waves-p2p"
+        bits = 0
+        for i, (t, used) in enumerate(((keys, has_keys), (payload, has_keys), (staging, has_keys), (recv, receives), (recv_payload, receives))):
+            if used and t is not None and t.numel() and t.data_ptr() % 16:
+                bits |= 2 << i
+        return bits
+
     def sort(self, keys, staging, recv, payload=None, staging_payload=None, recv_payload=None, out=None, out_payload=None):
         """keys: this rank's shard (device tensor, left untouched).  staging: same length as keys (bucket-grouped copy).
         recv: capacity for the incoming keys (not used by "waves-p2p", which receives into its peer-visible buffer).
         out (optional, same capacity as recv): enables the pipelined paths, whose result lands there.  Returns the number of
         keys this rank ends up with; `result_in_out` says whether they are in `out` or inside the engine (engine.download /
-        copy_result)."""
+        copy_result).  Shards may differ in size from rank to rank, down to none.  keys, payload, staging, recv and recv_payload must
+        start on a 16-byte boundary (the engine reads them 16 bytes per lane): if one rank's does not, EVERY rank raises
+        MisalignedBufferError (a ValueError) in this step, before any key moves."""
         n = keys.numel()
         self.result_in_out = False
         self._marks = []
@@ -359,9 +384,12 @@ class ShardedSorter:
         self._caps = (cap(recv, recv_payload), cap(out, out_payload))
         if self.strategy == "waves-p2p" and self._peer is not None:
             self._caps = (self._peer["capacity"], self._caps[1])      # what this rank receives into is its peer-visible buffer
-        self._status = self._engine_status()
+        local = self.world == 1 and not self.force_exchange
+        # a misaligned buffer is refused by the engine on THIS rank only: found here, before the first collective, it travels in the status word
+        # and no engine call sees the buffer (the paths below count nothing on a rank whose status is set)
+        self._status = self._engine_status() | self._misaligned(keys, payload, staging, None if local else recv, None if local else recv_payload)
         self._mark("start")
-        if self.world == 1 and not self.force_exchange:
+        if local:
             _raise_together([self._status])
             self.engine.sort_from(keys.data_ptr(), n, payload.data_ptr() if payload is not None else None)
             self.last_path = "local"
@@ -387,7 +415,8 @@ class ShardedSorter:
         if self.strategy == "top" or (self.strategy == "auto" and top_worth_a_try):
             # buckets on the top 4 key bits, if they deal out evenly
             top_shift = self.key_bits - TOP_BITS
-            table, caps = gather_counts(self.engine.partition_count(keys.data_ptr(), n, top_shift, TOP_BITS), self.world, self.dist, keys.device, self._caps, self._status)
+            counts = [0] * RADIX if self._status else self.engine.partition_count(keys.data_ptr(), n, top_shift, TOP_BITS)
+            table, caps = gather_counts(counts, self.world, self.dist, keys.device, self._caps, self._status)
             self._status = 0
             plan, imbalance = plan_from_table(table, self.rank, self.world)
             self._mark("count+plan")
@@ -399,7 +428,7 @@ class ShardedSorter:
                 return self._exchange_and_sort(plan, n, staging, recv, payload, staging_payload, recv_payload)
         if self.strategy == "split" or (self.strategy == "auto" and self.world <= MAX_SPLITTERS + 1):
             return self._sort_by_splitters(keys, n, staging, recv, payload, staging_payload, recv_payload, pay_in, pay_st)
-        lo, hi = self.engine.key_range(keys.data_ptr(), n)
+        lo, hi = ((1 << 64) - 1, 0) if self._status else self.engine.key_range(keys.data_ptr(), n)
         lo, hi = global_key_range(lo, hi, self.world, self.dist, keys.device, self._status)
         self._status = 0
         if lo >= hi:
@@ -466,12 +495,13 @@ class ShardedSorter:
         itemsize = self.key_bits // 8
         groups = wave_groups(k, self.grouping) if self.can_wave else []
         row, table = self._rows(keys.device)
-        self.engine.msd_count(keys.data_ptr(), n, bits, world, row.data_ptr())
+        counted = 0 if self._status else n          # a rank that will stop everybody (its status word says why) counts and scatters nothing
+        self.engine.msd_count(keys.data_ptr(), counted, bits, world, row.data_ptr())
         self._mark("count")
         # (the all_gather is also the step's opening barrier: it completes only once every rank has enqueued its own, behind the local
         # sorts of its previous step — nobody is still reading a receive buffer this step is about to write into)
         work = self.dist.all_gather_into_tensor(table, row, async_op=True)
-        self.engine.msd_scatter(keys.data_ptr(), n, staging.data_ptr(), pay_in, pay_st)          # needs only this rank's counts: runs beside the all_gather
+        self.engine.msd_scatter(keys.data_ptr(), counted, staging.data_ptr(), pay_in, pay_st)    # needs only this rank's counts: runs beside the all_gather
         self._mark("scatter")
         if p2p:
             return self._finish_waves_p2p(work, table, keys, staging, staging_payload, payload, out, out_payload, k, groups, itemsize)
@@ -483,7 +513,9 @@ class ShardedSorter:
         imbalance = max(loads) / max(1.0, sum(loads) / world)
         fits = True
         try:
-            check_capacity(loads, caps, need_out=True, slack=4 * k)     # each wave starts 16-byte aligned in recv
+            # the receive buffer holds the layout's extent (alignment gaps included), the output buffer the keys: the verdict of the C++
+            # driver and of the peer-store path's device plan
+            check_capacity_extent(wave_extents(counts, world, nb, 4, self.grouping), loads, caps)
         except CapacityError:
             if self.strategy == "waves":
                 raise                                                   # on every rank alike
@@ -585,7 +617,8 @@ class ShardedSorter:
         self.last_imbalance = max(loads) / max(1.0, sum(loads) / world)
         if verdict:
             # every rank computed the same verdict from the same table; the pushes wrote nothing
-            _raise_together([(verdict >> (32 + r)) & 1 for r in range(world)])
+            if verdict >> 32:
+                _raise_together(table.view(world, ROW_LEN)[:, ROW_STATUS].tolist())      # the status words themselves say why
             bad = [r for r in range(world) if (verdict >> r) & 1]
             raise CapacityError(f"rank {bad[0]} would receive {loads[bad[0]]} keys but its buffers are too small (ranks {bad})")
         self._mark("plan")
@@ -614,7 +647,7 @@ class ShardedSorter:
 
     # -- one-shot paths -----------------------------------------------------------------------------------------------------
     def _sort_by_splitters(self, keys, n, staging, recv, payload, staging_payload, recv_payload, pay_in, pay_st):
-        count = min(SAMPLES_PER_RANK, n)
+        count = 0 if self._status else min(SAMPLES_PER_RANK, n)
         mine = self.engine.sample_keys(keys.data_ptr(), n, count) if count else []
         samples, sizes = gather_samples(mine, n, self.world, self.dist, keys.device, self._status)
         self._status = 0

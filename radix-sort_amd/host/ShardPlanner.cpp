@@ -370,6 +370,12 @@ int rsxh_plan_check_capacity(const std::uint64_t* loads, const std::uint64_t* re
                                      std::vector<std::uint64_t>(out_caps, out_caps + world), need_out != 0, slack);
 }
 
+int rsxh_plan_check_capacity_extent(const std::uint64_t* extents, const std::uint64_t* loads, const std::uint64_t* recv_caps, const std::uint64_t* out_caps, int world)
+{
+    return shardplan::check_capacity_extent(std::vector<std::uint64_t>(extents, extents + world), std::vector<std::uint64_t>(loads, loads + world),
+                                            std::vector<std::uint64_t>(recv_caps, recv_caps + world), std::vector<std::uint64_t>(out_caps, out_caps + world));
+}
+
 int rsxh_plan_peer_access(const std::int64_t* identities, int world, int my_rank, int* access_out)
 {
     if (!identities || !access_out || world < 1 || my_rank < 0 || my_rank >= world) return -1;

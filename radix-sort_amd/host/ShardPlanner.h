@@ -97,6 +97,8 @@ int rsxh_plan_split(const std::uint64_t* table, int world, int nbuckets, int ran
 int rsxh_plan_range_buckets(std::uint64_t lo, std::uint64_t hi, int key_bits, int* shift, std::uint64_t* mul);
 int rsxh_plan_check_capacity(const std::uint64_t* loads, const std::uint64_t* recv_caps, const std::uint64_t* out_caps, int world, int need_out,
                              std::uint64_t slack);
+// the pipelined paths' verdict: extents[r] (wave_layout's slots, alignment gaps included) against the receive capacity, loads[r] against the output capacity
+int rsxh_plan_check_capacity_extent(const std::uint64_t* extents, const std::uint64_t* loads, const std::uint64_t* recv_caps, const std::uint64_t* out_caps, int world);
 // identities: 4 x int64 per rank {host hash, process token, pid, device}; access_out: one PeerAccess value per rank; -1 on a rank of another host
 int rsxh_plan_peer_access(const std::int64_t* identities, int world, int my_rank, int* access_out);
 }

@@ -39,6 +39,7 @@ def _load() -> C.CDLL:
         "rsxh_plan_split": [U64P, I, I, I, U64P, U64P, U64P, C.POINTER(C.c_double)],
         "rsxh_plan_range_buckets": [U64, U64, I, C.POINTER(I), U64P],
         "rsxh_plan_check_capacity": [U64P, U64P, U64P, I, I, U64],
+        "rsxh_plan_check_capacity_extent": [U64P, U64P, U64P, U64P, I],
         "rsxh_plan_peer_access": [C.POINTER(C.c_int64), I, I, C.POINTER(I)],
     }
     for name, args in sig.items():
@@ -182,6 +183,15 @@ def check_capacity(loads: list[int], caps: list[tuple[int, int]], need_out: bool
     if bad >= 0:
         recv_cap, out_cap = caps[bad]
         raise CapacityError(f"rank {bad} would receive {loads[bad]} keys but its buffers hold {recv_cap} (receive) / {out_cap} (output)")
+
+
+def check_capacity_extent(extents: list[int], loads: list[int], caps: list[tuple[int, int]]) -> None:
+    """The pipelined paths' verdict (the C++ driver's and the device plan's): every rank's receive buffer holds the EXTENT of its wave
+    layout (wave_extents: the slots up to the end of its last wave, alignment gaps included), its output buffer holds its load."""
+    bad = _load().rsxh_plan_check_capacity_extent(_arr(extents), _arr(loads), _arr([c[0] for c in caps]), _arr([c[1] for c in caps]), len(loads))
+    if bad >= 0:
+        recv_cap, out_cap = caps[bad]
+        raise CapacityError(f"rank {bad} would receive {loads[bad]} keys (spanning {extents[bad]} slots) but its buffers hold {recv_cap} (receive) / {out_cap} (output)")
 
 
 def peer_access(identities: list[tuple[int, int, int, int]], my_rank: int) -> list[int]:

@@ -104,6 +104,13 @@ def check_capacity(loads: list[int], caps: list[tuple[int, int]], need_out: bool
             raise CapacityError(f"rank {r} would receive {load} keys but its buffers hold {recv_cap} (receive) / {out_cap} (output)")
 
 
+def check_capacity_extent(extents: list[int], loads: list[int], caps: list[tuple[int, int]]) -> None:
+    """The pipelined paths: the receive buffer must hold the wave layout's extent (alignment gaps included), the output buffer the load."""
+    for r, (extent, load, (recv_cap, out_cap)) in enumerate(zip(extents, loads, caps)):
+        if extent > recv_cap or load > out_cap:
+            raise CapacityError(f"rank {r} would receive {load} keys (spanning {extent} slots) but its buffers hold {recv_cap} (receive) / {out_cap} (output)")
+
+
 def plan_from_table(table: list[list[int]], rank: int, world_size: int) -> tuple[ExchangePlan, float]:
     """Exchange plan from the gathered count table plus the resulting imbalance
     (largest rank load / ideal load)."""

@@ -55,21 +55,34 @@ def test_bucket_owner_and_splits():
         d.bucket_owner(17)
 
 
+class _Refused(RuntimeError):
+    """What the HIP engine raises (RadixSortError) when the C ABI refuses an argument on the host."""
+
+
 class _CpuEngineDouble:
-    """Test double with the three engine methods ShardedSorter calls; operates on CPU torch
-    tensors through their data_ptr()."""
+    """Test double with the engine methods ShardedSorter calls; operates on CPU torch tensors through their data_ptr().  It refuses
+    a pointer that is not 16-byte aligned exactly where the C ABI does (rsx_capi.hip / capi_msd.inc: the buffers a kernel reads or
+    writes 16 bytes per lane, checked only when there are keys), so a driver that hands one over fails here as it would on the GPU."""
 
     def __init__(self, dtype):
         self.dtype = np.dtype(dtype)
         self.result = None
         self.result_payload = None
 
+    @staticmethod
+    def _need16(who, n, *ptrs):
+        if n > 0 and any(p is not None and p % 16 for p in ptrs):
+            raise _Refused(f"{who}: a buffer that must be 16-byte aligned is not")
+
     def _view(self, ptr, n, dtype):
         import ctypes as C
+        if n == 0:
+            return np.empty(0, dtype=dtype)
         buf = (C.c_char * (n * np.dtype(dtype).itemsize)).from_address(ptr)
         return np.frombuffer(buf, dtype=dtype, count=n)
 
     def partition(self, d_keys, n, shift, bits, d_keys_out, d_payload=None, d_payload_out=None):
+        self._need16("rsx_partition", n, d_keys, d_keys_out, d_payload)
         keys = self._view(d_keys, n, self.dtype)
         u = keys.view(np.uint32 if self.dtype.itemsize == 4 else np.uint64)
         if self.dtype.kind == "i":
@@ -89,6 +102,7 @@ class _CpuEngineDouble:
         return u
 
     def partition_count(self, d_keys, n, shift, bits):
+        self._need16("rsx_partition_count", n, d_keys)
         u = self._biased(self._view(d_keys, n, self.dtype))
         d = ((u >> u.dtype.type(shift)) & u.dtype.type((1 << bits) - 1)).astype(np.int64)
         self._counted = (d_keys, n, shift, bits)
@@ -96,15 +110,18 @@ class _CpuEngineDouble:
 
     def partition_scatter(self, d_keys, n, shift, bits, d_keys_out, d_payload=None, d_payload_out=None):
         assert self._counted == (d_keys, n, shift, bits)
+        self._need16("rsx_partition_scatter", n, d_keys_out, d_payload)
         self.partition(d_keys, n, shift, bits, d_keys_out, d_payload, d_payload_out)
 
     def key_range(self, d_keys, n):
         if n == 0:
             return (1 << 64) - 1, 0
+        self._need16("rsx_key_range", n, d_keys)
         u = self._biased(self._view(d_keys, n, self.dtype))
         return int(u.min()), int(u.max())
 
     def partition_range(self, d_keys, n, lo, shift, mul, d_keys_out, d_payload=None, d_payload_out=None):
+        self._need16("rsx_partition_range", n, d_keys, d_keys_out, d_payload)
         keys = self._view(d_keys, n, self.dtype)
         bits = self.dtype.itemsize * 8
         x = [int(v) - lo for v in self._biased(keys)]
@@ -117,6 +134,7 @@ class _CpuEngineDouble:
 
     def msd_count(self, d_keys, n, bits, world, d_counts):
         """rsx_msd_count: the 2^bits bucket sizes of the top `bits` bits into the caller's row (256 slots, natural order)."""
+        self._need16("rsx_msd_count", n, d_keys)
         u = self._biased(self._view(d_keys, n, self.dtype))
         kb = self.dtype.itemsize * 8
         top = (u >> u.dtype.type(kb - 8)).astype(np.int64)
@@ -128,6 +146,7 @@ class _CpuEngineDouble:
 
     def msd_scatter(self, d_keys, n, d_staging, d_payload=None, d_staging_payload=None):
         assert self._msd[:2] == (d_keys, n)
+        self._need16("rsx_msd_scatter", n, d_staging, d_payload)
         keys = self._view(d_keys, n, self.dtype)
         order = np.argsort(self._msd[2], kind="stable")
         self._view(d_staging, n, self.dtype)[:] = keys[order]
@@ -135,6 +154,7 @@ class _CpuEngineDouble:
             self._view(d_staging_payload, n, np.uint32)[:] = self._view(d_payload, n, np.uint32)[order]
 
     def sort_from_to(self, d_keys, n, first_pass, last_pass, d_keys_out, d_payload=None, d_payload_out=None):
+        self._need16("rsx_sort_from", n, d_keys, d_payload)             # (the output may sit anywhere)
         keys = self._view(d_keys, n, self.dtype).copy()
         u = self._biased(keys)
         low = u & u.dtype.type((1 << (4 * last_pass)) - 1)          # only the passes asked for
@@ -154,12 +174,14 @@ class _CpuEngineDouble:
 
     def partition_count_split(self, d_keys, n, splitters):
         assert 1 <= len(splitters) <= 7 and splitters == sorted(set(splitters))
+        self._need16("rsx_partition_count_split", n, d_keys)
         self._split = (d_keys, n, list(splitters))
         d = self._split_buckets(self._biased(self._view(d_keys, n, self.dtype)), splitters)
         return [int(v) for v in np.bincount(d, minlength=2 * len(splitters) + 1)]
 
     def partition_scatter_split(self, d_keys, n, d_keys_out, d_payload=None, d_payload_out=None):
         assert self._split[:2] == (d_keys, n)
+        self._need16("rsx_partition_scatter_split", n, d_keys_out, d_payload)
         keys = self._view(d_keys, n, self.dtype)
         order = np.argsort(self._split_buckets(self._biased(keys), self._split[2]), kind="stable")
         self._view(d_keys_out, n, self.dtype)[:] = keys[order]
@@ -167,10 +189,11 @@ class _CpuEngineDouble:
             self._view(d_payload_out, n, np.uint32)[:] = self._view(d_payload, n, np.uint32)[order]
 
     def sort_from(self, d_keys, n, d_payload=None):
+        self._need16("rsx_sort_from", n, d_keys, d_payload)
         keys = self._view(d_keys, n, self.dtype).copy()
         order = np.argsort(keys, kind="stable")
         self.result = keys[order]
-        if d_payload:
+        if d_payload or n == 0:          # (an empty payload tensor has no address)
             self.result_payload = self._view(d_payload, n, np.uint32).copy()[order]
 
 
@@ -199,7 +222,19 @@ def _make_full(kind, dtype, n, orc):
     return orc.dataset(kind, dtype, n, seed=77)
 
 
-def _worker(rank, world, port, dtype, kind, with_payload, n_per_rank, q, strategy="auto", partition_bits=None, grouping="doubling"):
+def _aligned_view(values, offset=0):
+    """A CPU tensor holding `values` that starts `offset` elements past a 64-byte boundary (torch's CPU allocator aligns to 64)."""
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(values))
+    buf = torch.empty(t.numel() + offset + 1, dtype=t.dtype)
+    view = buf[offset:offset + t.numel()]
+    view.copy_(t)
+    assert buf.data_ptr() % 64 == 0
+    return view
+
+
+def _worker(rank, world, port, dtype, kind, with_payload, n_per_rank, q, strategy="auto", partition_bits=None, grouping="doubling", sizes=None, caps=None):
+    """sizes: every rank's shard size (default n_per_rank each).  caps: every rank's (receive, output) capacity in keys (default: all keys)."""
     import torch
     import torch.distributed as dist
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -209,23 +244,27 @@ def _worker(rank, world, port, dtype, kind, with_payload, n_per_rank, q, strateg
         d = _dist_module()
         from _oracle import Oracle
         orc = Oracle()
-        full = _make_full(kind, dtype, n_per_rank * world, orc)
-        shard = full[rank * n_per_rank:(rank + 1) * n_per_rank].copy()
+        sizes = sizes or [n_per_rank] * world
+        total = sum(sizes)
+        first = sum(sizes[:rank])
+        full = _make_full(kind, dtype, total, orc)
+        shard = full[first:first + sizes[rank]]
         signed = {"uint32": np.int32, "uint64": np.int64}.get(np.dtype(dtype).name)
-        t_keys = torch.from_numpy(shard.view(signed) if signed else shard)
+        t_keys = _aligned_view(shard.view(signed) if signed else shard)
         staging = torch.empty_like(t_keys)
-        recv = torch.empty(n_per_rank * world, dtype=t_keys.dtype)
+        recv_cap, out_cap = caps[rank] if caps else (total, total)
+        recv = torch.empty(recv_cap, dtype=t_keys.dtype)
         pay = spay = rpay = None
         if with_payload:
-            pay = torch.arange(rank * n_per_rank, (rank + 1) * n_per_rank, dtype=torch.int32)
+            pay = torch.arange(first, first + sizes[rank], dtype=torch.int32)
             spay = torch.empty_like(pay)
-            rpay = torch.empty(n_per_rank * world, dtype=torch.int32)
+            rpay = torch.empty(recv_cap, dtype=torch.int32)
         eng = _CpuEngineDouble(dtype)
         sorter = d.ShardedSorter(eng, rank, world, np.dtype(dtype).itemsize * 8, dist, strategy=strategy, partition_bits=partition_bits, wave_grouping=grouping)
         out = opay = None
         if strategy in ("auto", "waves"):
-            out = torch.empty_like(recv)
-            opay = torch.empty_like(rpay) if with_payload else None
+            out = torch.empty(out_cap, dtype=t_keys.dtype)
+            opay = torch.empty(out_cap, dtype=torch.int32) if with_payload else None
         n_local = sorter.sort(t_keys, staging, recv, pay, spay, rpay, out, opay)
         if sorter.result_in_out:
             res = out[:n_local].numpy().view(np.dtype(dtype)).copy()
@@ -275,33 +314,146 @@ def test_sharded_sort_partition_bits(world, dtype, with_payload, bits, grouping)
     _run_world(world, dtype, "SeededUniform", with_payload, "waves", partition_bits=bits, grouping=grouping)
 
 
-def _run_world(world, dtype, kind, with_payload, strategy, partition_bits=None, grouping="doubling"):
+def _start_world(world, target, before_q, after_q=(), timeout=180):
+    """One process per rank; every rank's queue item (sorted by rank), or a failure if some rank has not answered in `timeout`
+    seconds (a rank left hanging in a collective) — the processes are killed either way, nothing outlives the test."""
+    import queue
     import torch.multiprocessing as mp
-    from _oracle import Oracle
-    n_per_rank = 3000
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, dtype, kind, with_payload, n_per_rank, q, strategy, partition_bits, grouping)) for r in range(world)]
-    for p in procs:
-        p.start()
-    outs = sorted((q.get(timeout=180) for _ in range(world)), key=lambda t: t[0])
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    procs = [ctx.Process(target=target, args=(r, world, port) + tuple(before_q) + (q,) + tuple(after_q)) for r in range(world)]
+    try:
+        for p in procs:
+            p.start()
+        try:
+            outs = sorted((q.get(timeout=timeout) for _ in range(world)), key=lambda t: t[0])
+        except queue.Empty:
+            pytest.fail(f"a rank did not finish within {timeout} s: the others are left hanging in a collective")
+        for p in procs:
+            p.join(timeout=60)
+            assert p.exitcode == 0
+        return outs
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.kill()
+                p.join(timeout=10)
+
+
+def _run_world(world, dtype, kind, with_payload, strategy, partition_bits=None, grouping="doubling", sizes=None, caps=None):
+    from _oracle import Oracle
+    n_per_rank = 3000
+    outs = _start_world(world, _worker, (dtype, kind, with_payload, n_per_rank), (strategy, partition_bits, grouping, sizes, caps))
     orc = Oracle()
-    full = _make_full(kind, dtype, n_per_rank * world, orc)
+    total = sum(sizes) if sizes else n_per_rank * world
+    full = _make_full(kind, dtype, total, orc)
     got = np.concatenate([o[2] for o in outs])
     assert sum(o[1] for o in outs) == full.size
     assert np.array_equal(got, np.sort(full, kind="stable"))
     assert len({o[4] for o in outs}) == 1                          # all ranks took the same path
-    if strategy == "auto":
+    if strategy == "auto" and sizes is None:
         assert outs[0][4] == ("waves" if kind == "SeededUniform" else "split")
-    if kind in ("Range", "InvertedRange", "SeededUniform") or strategy != "range":
+    if sizes is not None:
+        if strategy != "range":
+            assert max(o[1] for o in outs) <= 1.25 * total / world + 16     # balanced on the TOTAL, whatever each rank brought (+ a granule)
+    elif kind in ("Range", "InvertedRange", "SeededUniform") or strategy != "range":
         assert max(o[1] for o in outs) <= 1.2 * full.size / world        # the ranks stay balanced
     if with_payload:
         got_p = np.concatenate([o[3] for o in outs])
         assert np.array_equal(got_p, np.argsort(full, kind="stable").astype(np.uint32))   # global stable argsort
+
+
+@pytest.mark.parametrize("world,sizes,dtype,kind,with_payload,strategy,grouping", [
+    (4, [0, 3000, 3000, 3000], "uint32", "SeededUniform", True, "auto", "doubling"),      # one empty rank
+    (4, [9000, 0, 0, 0], "int64", "SeededUniform", True, "waves", "single"),              # one rank holds everything
+    (4, [0, 0, 0, 0], "uint32", "SeededUniform", True, "auto", "doubling"),               # nobody has keys
+    (4, [0, 0, 0, 0], "int32", "SeededUniform", False, "split", "doubling"),
+    (4, [0, 0, 0, 0], "uint64", "SeededUniform", True, "range", "doubling"),
+    (4, [1, 2, 3, 5], "int32", "SeededUniform", True, "auto", "doubling"),                # tiny, not multiples of 4
+    (4, [1, 2, 3, 5], "uint64", "HeavyTies", True, "split", "doubling"),
+    (4, [4095, 4096, 4097, 1], "uint32", "SeededUniform", True, "top", "doubling"),
+    (3, [0, 5000, 17], "int64", "HeavyTies", True, "auto", "doubling"),                   # not a power of two: the splitter path
+    (3, [7, 0, 4000], "uint32", "Zeros", False, "range", "doubling"),                     # every key equal: the range path's shortcut
+    (8, [0, 5, 6000, 0, 300, 1, 8191, 2], "uint32", "Skewed", True, "auto", "doubling"),
+    (2, [0, 6001], "int64", "Skewed", False, "range", "doubling"),
+])
+def test_uneven_shards(world, sizes, dtype, kind, with_payload, strategy, grouping):
+    """Shards of different sizes, down to none: the rank-order concatenation is still the stable sort (and argsort) of all keys,
+    every rank takes the same path and the loads are balanced on the total."""
+    _run_world(world, dtype, kind, with_payload, strategy, grouping=grouping, sizes=sizes)
+
+
+@pytest.mark.parametrize("grouping,dtype,with_payload", [("doubling", "uint32", True), ("doubling", "int64", False), ("single", "uint32", False)])
+def test_waves_fit_a_receive_buffer_of_exactly_the_extent(grouping, dtype, with_payload):
+    """strategy="waves" with every rank's receive buffer exactly as large as the extent of its wave layout (wave_extents: up to the end of its
+    last wave, alignment gaps included) and its output buffer exactly its load: the plan fits — the verdict of the C++ driver and of the
+    device plan — and sorts.  With doubling groups only the groups start aligned, so the extent is below load + 4 x waves."""
+    d = _dist_module()
+    from _oracle import Oracle
+    world, bits, sizes = 4, 6, [1001, 2999, 7, 3000]
+    k = (1 << bits) // world
+    full = _make_full("SeededUniform", dtype, sum(sizes), Oracle())
+    u = full.view(np.uint32 if full.dtype.itemsize == 4 else np.uint64)
+    if full.dtype.kind == "i":
+        u = u ^ u.dtype.type(1 << (full.dtype.itemsize * 8 - 1))
+    top = (u >> u.dtype.type(full.dtype.itemsize * 8 - bits)).astype(np.int64)
+    bounds = np.cumsum([0] + sizes)
+    table = [[int(v) for v in np.bincount(top[bounds[r]:bounds[r + 1]], minlength=1 << bits)] for r in range(world)]
+    g = d.GROUP_DOUBLING if grouping == "doubling" else d.GROUP_SINGLE
+    _, _, loads = d.wave_layout(table, world, 1 << bits, 4, g)
+    extents = d.wave_extents(table, world, 1 << bits, 4, g)
+    assert all(e >= l for e, l in zip(extents, loads))
+    if grouping == "doubling":
+        assert all(e < l + 4 * k for e, l in zip(extents, loads))        # the old rule (load + 4 x waves) refused every rank
+    _run_world(world, dtype, "SeededUniform", with_payload, "waves", partition_bits=bits, grouping=grouping, sizes=sizes, caps=list(zip(extents, loads)))
+
+
+def _misaligned_worker(rank, world, port, strategy, which, q):
+    """Rank 1 hands over its keys (or its payload) as a view one element past a 16-byte boundary; every rank reports what it raised."""
+    import torch
+    import torch.distributed as dist
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        d = _dist_module()
+        from _oracle import Oracle
+        n = 3001
+        full = Oracle().dataset("SeededUniform", "uint32", n * world, seed=9)
+        odd = rank == 1
+        keys = _aligned_view(full[rank * n:(rank + 1) * n].view(np.int32), 1 if odd and which == "keys" else 0)
+        pay = _aligned_view(np.arange(rank * n, (rank + 1) * n, dtype=np.int32), 1 if odd and which == "payload" else 0)
+        assert (keys.data_ptr() % 16 != 0) == (odd and which == "keys") and (pay.data_ptr() % 16 != 0) == (odd and which == "payload")
+        staging, spay = torch.empty_like(keys), torch.empty_like(pay)
+        recv, rpay = torch.empty(n * world, dtype=keys.dtype), torch.empty(n * world, dtype=torch.int32)
+        out, opay = torch.empty_like(recv), torch.empty_like(rpay)
+        sorter = d.ShardedSorter(_CpuEngineDouble("uint32"), rank, world, 32, dist, strategy=strategy)
+        outcomes = []
+        for _ in range(2):                                   # the second step, with aligned buffers everywhere, runs
+            try:
+                sorter.sort(keys, staging, recv, pay, spay, rpay, out, opay)
+                outcomes.append("sorted")
+            except ValueError as exc:
+                outcomes.append(f"{type(exc).__name__}:{exc}")
+            dist.barrier()                                   # every rank is still in step: nobody is stuck in a collective
+            keys, pay = _aligned_view(keys.numpy()), _aligned_view(pay.numpy())
+        q.put((rank, outcomes))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("strategy", ["auto", "waves", "top", "split", "range"])
+@pytest.mark.parametrize("which", ["keys", "payload"])
+def test_misaligned_shard_raises_on_every_rank(strategy, which):
+    """One rank's shard (or its payload) does not start on a 16-byte boundary, which the engine refuses on that rank alone: the driver finds
+    it before its first collective, the status word carries it, and EVERY rank raises the same MisalignedBufferError naming the rank and
+    the buffer — nobody is left waiting in a collective, and no engine call (no kernel) ever sees the pointer."""
+    outs = _start_world(2, _misaligned_worker, (strategy, which), timeout=90)
+    for _, outcomes in outs:
+        assert outcomes[0] == f"MisalignedBufferError:buffers that are not 16-byte aligned: rank 1 {which} (the engine reads them 16 bytes per lane); " \
+                              "every rank stops here together", outs
+        assert outcomes[1] == "sorted", outs
 
 
 def test_choose_splitters_and_split_plan():

@@ -176,3 +176,104 @@ def test_plan_verdict_when_a_rank_is_too_small(rsx, oracle):
     finally:
         for e in engines:
             e.close()
+
+
+@pytest.mark.parametrize("dt,bits,world,payload,grouping,sizes", [
+    ("uint32", 6, 8, False, 1, [0, 1, 2, 3, 6000, 30011, 4096, 777]),
+    ("int64", 8, 4, True, 0, [3, 0, 20000, 1]),
+    ("int32", 5, 4, True, 1, [2, 4097, 0, 12345]),
+    ("uint64", 4, 2, False, 0, [9999, 1]),
+    ("uint32", 8, 16, True, 1, [0, 3, 1, 2, 0, 5000, 0, 0, 64, 0, 0, 7, 4095, 0, 0, 1]),
+])
+def test_device_plan_with_uneven_shards_and_exact_capacities(rsx, oracle, dt, bits, world, payload, grouping, sizes):
+    """The exchange kernels with shards of different sizes (0, 1, 2, 3 keys, and a shard whose keys all fall into ONE fine bucket) and every
+    receive buffer exactly as large as the extent of its wave layout (host planner's wave_extents), every output capacity exactly its load:
+    the device plan says go, loads / wave starts / wave counts equal the host planner's, every key lands in its slot up to the last one and
+    the sentinel slots behind the extent stay untouched.  Then one rank's capacity is one slot short: every rank's plan carries verdict
+    1 << r and no push writes a byte anywhere."""
+    import torch
+    from radix_sort_amd import planner
+    stride, sentinel = 259, 8
+    total = sum(sizes)
+    full = oracle.dataset("SeededUniform", dt, total, seed=bits * 7 + world)
+    u_all, kb = _unsigned(full)
+    bounds = np.cumsum([0] + sizes)
+    one = max(range(world), key=lambda r: (sizes[r] >= 4, r == world // 2))        # this shard's keys share one top byte
+    lo, hi = int(bounds[one]), int(bounds[one + 1])
+    raw = full.view(u_all.dtype)
+    raw[lo:hi] = (raw[lo:hi] & u_all.dtype.type((1 << (kb - 8)) - 1)) | u_all.dtype.type(0x5A << (kb - 8))
+    u_all, _ = _unsigned(full)
+    signed = {"uint32": np.int32, "uint64": np.int64}.get(np.dtype(dt).name)
+    tdt = torch.int32 if kb == 32 else torch.int64
+    waves = (1 << bits) // world
+    top_all = (u_all >> u_all.dtype.type(kb - bits)).astype(np.int64)
+    counts = [[int(v) for v in np.bincount(top_all[bounds[r]:bounds[r + 1]], minlength=1 << bits)] for r in range(world)]
+    assert sum(c > 0 for c in counts[one]) == (1 if sizes[one] else 0)
+    start, offset, loads = planner.wave_layout(counts, world, 1 << bits, 4, grouping)
+    extents = planner.wave_extents(counts, world, 1 << bits, 4, grouping)
+    table = torch.zeros(world * stride, dtype=torch.int64, device="cuda")
+    engines = [rsx.Engine(dt, max(n, 16), payload=payload) for n in sizes]
+    try:
+        stagings, spays, recvs, rpays = [], [], [], []
+        for r, e in enumerate(engines):
+            e.set_stream(torch.cuda.current_stream().cuda_stream)
+            shard = full[bounds[r]:bounds[r + 1]]
+            tk = torch.from_numpy((shard.view(signed) if signed else shard).copy()).cuda()
+            pay = torch.arange(int(bounds[r]), int(bounds[r + 1]), dtype=torch.int32, device="cuda") if payload else None
+            stagings.append(torch.empty_like(tk))
+            spays.append(torch.empty_like(pay) if payload else None)
+            recvs.append(torch.full((extents[r] + sentinel,), -7, dtype=tdt, device="cuda"))
+            rpays.append(torch.full((extents[r] + sentinel,), -7, dtype=torch.int32, device="cuda") if payload else None)
+            e.msd_count(tk.data_ptr(), sizes[r], bits, world, table[r * stride:].data_ptr())
+            e.msd_scatter(tk.data_ptr(), sizes[r], stagings[r].data_ptr(), pay.data_ptr() if payload else None, spays[r].data_ptr() if payload else None)
+        torch.cuda.synchronize()
+        assert [[int(v) for v in row[:1 << bits]] for row in table.cpu().view(world, stride).tolist()] == counts
+        peer_k = torch.tensor([t.data_ptr() for t in recvs], dtype=torch.int64, device="cuda")
+        peer_p = torch.tensor([t.data_ptr() for t in rpays], dtype=torch.int64, device="cuda") if payload else None
+
+        def step(caps):
+            for r in range(world):
+                table[r * stride + 256], table[r * stride + 257] = caps[r]
+            plans = []
+            for r, e in enumerate(engines):
+                e.msd_plan(table.data_ptr(), stride, 256, r, 0, grouping)
+                plans.append(e.msd_plan_wait(waves, world))
+                for w in range(waves):
+                    e.msd_push(w, stagings[r].data_ptr(), peer_k.data_ptr(), spays[r].data_ptr() if payload else None, peer_p.data_ptr() if payload else None)
+            torch.cuda.synchronize()
+            return plans
+
+        plans = step(list(zip(extents, loads)))
+        for d in range(world):
+            ws, wc, ld, verdict = plans[d]
+            assert verdict == 0 and ld == loads and ws == start[d]
+            assert wc == [sum(counts[s][d * waves + w] for s in range(world)) for w in range(waves)]
+            got = recvs[d].cpu().numpy().view(full.dtype)
+            gotp = rpays[d].cpu().numpy().view(np.uint32) if payload else None
+            used = np.zeros(extents[d] + sentinel, dtype=bool)
+            for w in range(waves):
+                for s in range(world):
+                    idx = np.flatnonzero(top_all[bounds[s]:bounds[s + 1]] == d * waves + w) + bounds[s]
+                    sub = (u_all[idx] >> u_all.dtype.type(kb - 8)).astype(np.int64)
+                    idx = idx[np.argsort(sub, kind="stable")]
+                    at = offset[d][w][s]
+                    assert at + idx.size <= extents[d]
+                    assert np.array_equal(got[at:at + idx.size], full[idx]), (d, w, s)
+                    if payload:
+                        assert np.array_equal(gotp[at:at + idx.size], idx.astype(np.uint32)), (d, w, s)
+                    used[at:at + idx.size] = True
+            assert used.sum() == loads[d]
+            assert (recvs[d].cpu().numpy()[~used] == -7).all()                              # gaps and the sentinel behind the extent untouched
+            if payload:
+                assert (rpays[d].cpu().numpy()[~used] == -7).all()
+        # one slot short on one rank (the one with the largest extent): the same verdict everywhere, nothing written
+        short = max(range(world), key=lambda r: extents[r])
+        for t in recvs + [p for p in rpays if p is not None]:
+            t.fill_(-7)
+        plans = step([(e - (r == short), l) for r, (e, l) in enumerate(zip(extents, loads))])
+        assert all(p[3] == 1 << short for p in plans), [p[3] for p in plans]
+        for t in recvs + [p for p in rpays if p is not None]:
+            assert (t == -7).all()
+    finally:
+        for e in engines:
+            e.close()

@@ -19,9 +19,9 @@ class _Loopback:
     blocking call, before the call returns).  A sorter that forgot a wait, or whose engine ran on a
     stream other than torch's current one, therefore races here exactly as it would on 8 GPUs."""
 
-    def __init__(self, world):
+    def __init__(self, world, timeout=None):
         self.world = world
-        self.barrier = threading.Barrier(world)
+        self.barrier = threading.Barrier(world, timeout=timeout)     # timeout: a rank left waiting fails (BrokenBarrierError) instead of hanging
         self.slots = [None] * world
         self.done = [None] * world
 
@@ -634,3 +634,201 @@ def test_bench_peer_store_exchange_between_rank_processes(ranks, extra):
     assert line["config"]["verified"].startswith("bit-exact vs a host sort of all")
     assert "[waves-p2p]" in line["config"]["parallelism"] and "peer stores" in line["config"]["parallelism"]
     assert set(line["sharded_phases_ms"]) - {"note"} <= {"count", "scatter", "plan", "fence", "local_sort"}
+
+
+# --------------------------------------------------------------------------- shards of different sizes, down to none
+def _thread_ranks(rsx, full, sizes, dtype, with_payload, strategy, bits=None, grouping="doubling", radix_bits=4, caps=None, offsets=None):
+    """One step of the sharded sort with rank r holding the r-th contiguous piece of `full` of sizes[r] keys (rank threads on the one
+    GPU, the loopback hub with a barrier timeout).  caps[r]: (receive, output) capacity in keys (default: all keys plus the waves'
+    alignment gaps, 4 slots per wave at most).  offsets: {rank: ("keys" | "payload", elements)} hands that buffer over as a view that far
+    past an aligned start.  Returns per rank (keys, payload, path, result) where result is the number of keys or the exception raised."""
+    import torch
+    from radix_sort_amd.distributed import ShardedSorter
+    world, total = len(sizes), sum(sizes)
+    bounds = np.cumsum([0] + list(sizes))
+    hub = _Loopback(world, timeout=120)
+    results, errors = [None] * world, []
+    signed = {"uint32": np.int32, "uint64": np.int64}.get(np.dtype(dtype).name)
+    p2p = strategy == "waves-p2p"
+
+    def placed(t, rank, which):
+        off = (offsets or {}).get(rank, (None, 0))
+        if off[0] != which or off[1] == 0:
+            return t
+        buf = torch.empty(t.numel() + off[1], dtype=t.dtype, device=t.device)
+        buf[off[1]:].copy_(t)
+        return buf[off[1]:]
+
+    def run(rank):
+        try:
+            lo, hi = int(bounds[rank]), int(bounds[rank + 1])
+            shard = full[lo:hi].copy()
+            recv_cap, out_cap = caps[rank] if caps else (total + 4 * 256, total + 4 * 256)
+            stream = torch.cuda.Stream()
+            with torch.cuda.stream(stream):
+                keys = placed(torch.from_numpy(shard.view(signed) if signed else shard).cuda(), rank, "keys")
+                staging = torch.empty_like(keys)
+                recv = None if p2p else torch.empty(recv_cap, dtype=keys.dtype, device="cuda")
+                obuf = torch.empty(out_cap, dtype=keys.dtype, device="cuda")
+                pay = spay = rpay = opay = None
+                if with_payload:
+                    pay = placed(torch.arange(lo, hi, dtype=torch.int32, device="cuda"), rank, "payload")
+                    spay = torch.empty_like(pay)
+                    rpay = None if p2p else torch.empty(recv_cap, dtype=torch.int32, device="cuda")
+                    opay = torch.empty(out_cap, dtype=torch.int32, device="cuda")
+                with rsx.Engine(dtype, max(total + 4 * 256, 16), payload=with_payload) as eng:
+                    eng.set_stream(stream.cuda_stream)
+                    if radix_bits != 4:
+                        eng.set_option(rsx.OPT_RADIX_BITS, radix_bits)
+                    sorter = ShardedSorter(eng, rank, world, np.dtype(dtype).itemsize * 8, hub.view(rank), strategy=strategy, partition_bits=bits,
+                                           wave_grouping=grouping, force_exchange=True)
+                    if p2p:
+                        sorter.setup_peer_exchange(recv_cap, keys.device, with_payload)
+                    try:
+                        try:
+                            n_local = sorter.sort(keys, staging, recv, pay, spay, rpay, obuf, opay)
+                        except (ValueError, RuntimeError) as exc:
+                            if isinstance(exc, threading.BrokenBarrierError):
+                                raise
+                            torch.cuda.synchronize()
+                            results[rank] = (None, None, sorter.last_path, exc)
+                            return
+                        eng.sync()                               # reports a timed-out table scan, if any
+                        if sorter.result_in_out:
+                            out = (obuf[:n_local].cpu().numpy().view(np.dtype(dtype)), opay[:n_local].cpu().numpy().view(np.uint32) if with_payload else None)
+                        else:
+                            out = eng.download(want_perm=True) if with_payload else (eng.download(), None)
+                        results[rank] = (out[0], out[1], sorter.last_path, n_local)
+                    finally:
+                        if p2p:
+                            sorter.close_peer_exchange()
+        except Exception as exc:   # noqa: BLE001 - surface in the main thread
+            errors.append(exc)
+            hub.barrier.abort()
+
+    threads = [threading.Thread(target=run, args=(r,)) for r in range(world)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(timeout=300)
+    assert not any(t.is_alive() for t in threads), "a rank thread is still running"
+    assert not errors, errors
+    return results
+
+
+def _check_sorted(results, full, with_payload, strategy, world):
+    for r in results:
+        assert not isinstance(r[3], BaseException), results
+    assert sum(r[3] for r in results) == full.size
+    assert np.array_equal(np.concatenate([r[0] for r in results]), np.sort(full, kind="stable"))
+    if with_payload:
+        assert np.array_equal(np.concatenate([r[1] for r in results]), np.argsort(full, kind="stable").astype(np.uint32))
+    assert len({r[2] for r in results}) == 1, [r[2] for r in results]          # every rank took the same path
+    if strategy != "range":
+        assert max(r[3] for r in results) <= 1.25 * full.size / world + 16        # balanced on the TOTAL (+ one 16-key granule)
+
+
+def _sizes(spec, seed=0):
+    if spec == "random8":                 # world 8, seeded sizes in [0, 3n]
+        return [int(v) for v in np.random.default_rng(seed).integers(0, 3 * 20011 + 1, size=8)]
+    return list(spec)
+
+
+N = 100003
+# (sizes, dtype, distribution, payload, strategy[:partition bits[:grouping]], radix bits): a pairwise selection over shard shapes x strategies x key
+# types x payload x grouping x distributions.  The forced pipelined and top-bit strategies keep inputs whose top bits balance (they promise
+# no balance otherwise); the tile-sort boundary is 4096 keys, RSX_RADIX8_MIN_KEYS is 4096 under the suite's conftest.
+UNEVEN = [
+    ([0, N, N, N], "uint32", "SeededUniform", False, "auto", 4),
+    ([0, N, N, N], "int64", "HeavyTies", True, "auto", 4),
+    ([0, N, N, N], "uint64", "SeededUniform", True, "waves-p2p", 4),
+    ([0, N, N, N], "int32", "Skewed", True, "split", 4),
+    ([3 * N, 0, 0, 0], "int32", "SeededUniform", True, "waves", 4),
+    ([3 * N, 0, 0, 0], "uint64", "SeededUniform", False, "top", 4),
+    ([3 * N, 0, 0, 0], "uint32", "Zeros", True, "range", 4),
+    ([3 * N, 0, 0, 0], "int64", "SeededUniform", True, "waves-p2p:6:single", 8),
+    ([0, 0, 0, 0], "uint32", "SeededUniform", True, "auto", 4),
+    ([0, 0, 0, 0], "int64", "SeededUniform", False, "waves", 4),
+    ([0, 0, 0, 0], "uint64", "SeededUniform", True, "waves-p2p", 4),
+    ([0, 0, 0, 0], "int32", "SeededUniform", True, "split", 4),
+    ([0, 0, 0, 0], "uint32", "SeededUniform", False, "range", 4),
+    ([0, 0, 0, 0], "int64", "SeededUniform", True, "top", 4),
+    ([1, 2, 3, 5], "int32", "SeededUniform", True, "auto", 4),
+    ([1, 2, 3, 5], "uint32", "SeededUniform", True, "waves:8:single", 8),
+    ([1, 2, 3, 5], "uint64", "HeavyTies", False, "split", 4),
+    ([1, 2, 3, 5], "int64", "SeededUniform", True, "waves-p2p", 4),
+    ([1, 2, 3, 5], "uint32", "Zeros", True, "range", 4),
+    ([4095, 4096, 4097, 1], "uint32", "SeededUniform", True, "waves", 4),
+    ([4095, 4096, 4097, 1], "int64", "SeededUniform", False, "waves-p2p:8", 4),
+    ([4095, 4096, 4097, 1], "int32", "Skewed", True, "auto", 4),
+    ([4095, 4096, 4097, 1], "uint64", "SeededUniform", True, "top", 4),
+    ([16383, 16385, 4, 16384], "uint32", "SeededUniform", True, "waves:4", 8),        # waves of ~4096 keys: both sides of the 8-bit threshold
+    ([16383, 16385, 4, 16384], "int64", "SeededUniform", False, "waves-p2p:4:single", 8),
+    ([16383, 16385, 4, 16384], "int32", "HeavyTies", True, "auto", 8),
+    ("random8", "uint32", "SeededUniform", True, "auto", 4),
+    ("random8", "int64", "Skewed", False, "auto", 4),
+    ("random8", "uint64", "SeededUniform", True, "waves:6:single", 4),
+    ("random8", "int32", "SeededUniform", False, "waves-p2p", 8),
+    ("random8", "uint32", "HeavyTies", True, "range", 4),
+    ([0, 2 * N, 17], "uint32", "SeededUniform", True, "auto", 4),                     # world 3: the splitter path
+    ([5, 0, N], "int64", "Zeros", False, "auto", 4),
+    ([5, 0, N], "uint64", "Skewed", True, "range", 4),
+    ([0, 3, 40000, 0, 1, 9000, 0, 20000, 0, 0, 77, 4096, 0, 5, 12000, 0], "int32", "SeededUniform", True, "waves:8", 4),     # world 16, 16 waves per rank
+    ([0, 3, 40000, 0, 1, 9000, 0, 20000, 0, 0, 77, 4096, 0, 5, 12000, 0], "uint32", "SeededUniform", False, "waves-p2p:8", 4),
+]
+
+
+@pytest.mark.parametrize("sizes,dtype,kind,with_payload,strategy,radix_bits", UNEVEN)
+def test_uneven_shards_on_one_gpu(rsx, oracle, sizes, dtype, kind, with_payload, strategy, radix_bits):
+    """The sharded sort with shards of different sizes — one rank empty, one rank holding everything, nobody holding anything, a few keys
+    each, shards around the tile-sort boundary and the 8-bit threshold, random sizes — on every exchange strategy: the rank-order
+    concatenation is the stable sort (and argsort) of all keys, bit for bit, every rank takes the same path and the loads are balanced."""
+    strategy, bits, grouping = (strategy.split(":") + ["", ""])[:3]
+    sizes = _sizes(sizes, seed=len(UNEVEN))
+    full = _make_full(kind, dtype, sum(sizes), oracle)
+    results = _thread_ranks(rsx, full, sizes, dtype, with_payload, strategy, int(bits) if bits else None, grouping or "doubling", radix_bits)
+    _check_sorted(results, full, with_payload, strategy, len(sizes))
+    if strategy in ("waves", "waves-p2p", "top", "split", "range") and sum(sizes):
+        assert results[0][2] in (strategy, "equal"), results[0][2]
+    if not sum(sizes):
+        assert all(r[3] == 0 for r in results)
+
+
+@pytest.mark.parametrize("strategy,grouping,dtype,with_payload", [("waves", "doubling", "uint32", True), ("waves", "doubling", "int64", False),
+                                                                  ("waves-p2p", "doubling", "uint32", False), ("waves", "single", "int32", True)])
+def test_receive_buffers_of_exactly_the_extent(rsx, oracle, strategy, grouping, dtype, with_payload):
+    """Every rank's receive buffer exactly as large as the extent of its wave layout (planner.wave_extents: alignment gaps included) and its
+    output buffer exactly its load: the pipelined paths fit and sort bit-exact.  With doubling groups the extent is below load + 4 x waves,
+    where the Python driver's old rule raised CapacityError."""
+    from radix_sort_amd import planner
+    world, bits, sizes = 4, 6, [30001, 77, 49999, 4099]
+    full = _make_full("SeededUniform", dtype, sum(sizes), oracle)
+    u, kb = full.view(np.uint32 if full.dtype.itemsize == 4 else np.uint64), full.dtype.itemsize * 8
+    if full.dtype.kind == "i":
+        u = u ^ u.dtype.type(1 << (kb - 1))
+    top = (u >> u.dtype.type(kb - bits)).astype(np.int64)
+    bounds = np.cumsum([0] + sizes)
+    table = [[int(v) for v in np.bincount(top[bounds[r]:bounds[r + 1]], minlength=1 << bits)] for r in range(world)]
+    g = planner.GROUP_DOUBLING if grouping == "doubling" else planner.GROUP_SINGLE
+    _, _, loads = planner.wave_layout(table, world, 1 << bits, 4, g)
+    extents = planner.wave_extents(table, world, 1 << bits, 4, g)
+    if grouping == "doubling":
+        assert all(e < l + 4 * ((1 << bits) // world) for e, l in zip(extents, loads))
+    results = _thread_ranks(rsx, full, sizes, dtype, with_payload, strategy, bits, grouping, caps=list(zip(extents, loads)))
+    _check_sorted(results, full, with_payload, strategy, world)
+    assert results[0][2] == strategy
+
+
+@pytest.mark.parametrize("strategy,which,dtype", [("auto", "keys", "uint32"), ("waves", "payload", "int64"), ("waves-p2p", "keys", "int32"), ("waves-p2p", "payload", "uint32"),
+                                                  ("top", "keys", "uint64"), ("split", "payload", "uint32"), ("range", "keys", "int32")])
+def test_misaligned_shard_raises_on_every_rank_on_the_gpu(rsx, oracle, strategy, which, dtype):
+    """Rank 2 of four hands over its keys (or its payload) one element past a 16-byte boundary — what `full[r * n:(r + 1) * n]` with an odd n
+    gives.  The engine refuses such a pointer on that rank alone; the driver finds it before its first collective and EVERY rank raises the
+    same MisalignedBufferError, naming the rank and the buffer.  Nobody waits for a barrier that never comes, and no kernel sees the pointer."""
+    from radix_sort_amd.distributed import MisalignedBufferError
+    sizes = [20001, 20001, 20001, 20001]
+    full = _make_full("SeededUniform", dtype, sum(sizes), oracle)
+    results = _thread_ranks(rsx, full, sizes, dtype, True, strategy, offsets={2: (which, 1)})
+    for r in results:
+        assert isinstance(r[3], MisalignedBufferError), results
+        assert f"rank 2 {which}" in str(r[3]) and "rank 0" not in str(r[3]), str(r[3])

@@ -139,6 +139,51 @@ def test_splitters_range_buckets_and_capacity_match():
         assert outcomes[0] == outcomes[1]
 
 
+def _verdict(fn, *args):
+    try:
+        fn(*args)
+        return None
+    except RuntimeError as exc:
+        return str(exc)
+
+
+def test_capacity_verdict_of_the_pipelined_paths_is_the_extent():
+    """The waves paths fit when every receive buffer holds the EXTENT of its wave layout and every output buffer its load — the rule of
+    the C++ driver and of the device plan.  With doubling groups only the groups start aligned, so the extent is below load + 4 x waves:
+    capacity at the extent fits, one slot less does not, for the binding, the reference statement and the Python driver's decision
+    alike; the load + 4 x waves rule (what distributed.py used to apply) refuses the first."""
+    pl = _planner()
+    d = __import__("radix_sort_amd.distributed", fromlist=["ShardedSorter"])
+    rnd = random.Random(15)
+    cases = [(4, 64, [[0] * 64, [1] * 64, [2] * 64, [3] * 64]),                        # tiny, ragged segments inside every wave
+             (8, 64, [[rnd.choice([0, 1, 2, 3, 5, 7]) for _ in range(64)] for _ in range(8)]),
+             (2, 16, [[5] * 16, [0] * 16]),
+             (16, 256, [[rnd.randint(0, 40) for _ in range(256)] for _ in range(16)])]
+    cases += [(w, nb, _random_table(rnd, w, nb)) for _ in range(30) for w, nb in ((2, 16), (4, 32), (8, 64), (8, 256), (16, 128))]
+    checked = 0
+    for world, nb, table in cases:
+        k = nb // world
+        for grouping in (pl.GROUP_DOUBLING, pl.GROUP_SINGLE):
+            _, _, loads = pl.wave_layout(table, world, nb, 4, grouping)
+            extents = pl.wave_extents(table, world, nb, 4, grouping)
+            assert extents == ref.wave_layout(table, world, nb, 4, grouping)[3]
+            for r in range(world):
+                exact = list(zip(extents, loads))
+                tight_recv = [(e - 1, l) if i == r else (e, l) for i, (e, l) in enumerate(exact)]
+                tight_out = [(e, l - 1) if i == r else (e, l) for i, (e, l) in enumerate(exact)]
+                variants = [(exact, True)] + ([(tight_recv, False)] if extents[r] else []) + ([(tight_out, False)] if loads[r] else [])
+                for caps, fits in variants:
+                    got = _verdict(pl.check_capacity_extent, extents, loads, caps)
+                    assert got == _verdict(ref.check_capacity_extent, extents, loads, caps)
+                    assert (got is None) == fits and (fits or got.startswith(f"rank {r} would receive {loads[r]} keys"))
+                    assert got == _verdict(d.check_capacity_extent, extents, loads, caps)         # what the Python driver's waves path calls
+                    checked += 1
+            if grouping == pl.GROUP_DOUBLING and k > 2 and all(l > 0 for l in loads) and any(e < l + 4 * k for e, l in zip(extents, loads)):
+                # the rule the Python driver used to apply disagrees: it refuses a plan the C++ driver and the device plan run
+                assert _verdict(pl.check_capacity, loads, list(zip(extents, loads)), True, 4 * k) is not None
+    assert checked > 500
+
+
 def test_peer_access_decision():
     """How a rank reaches every other rank's receive buffer, from what everybody published about itself (host, process token, pid,
     device): threads of one process on one device share pointers, threads on ANOTHER device need rsx_peer_enable first, other
