@@ -51,6 +51,21 @@ typedef struct rsx_engine rsx_engine;   /* opaque */
 #define RSX_RADIX_BITS 4
 #define RSX_RADIX 16
 
+/* Key kinds of rsx_create.  Keys are ordered by the unsigned value of their ENCODING, B = key width in bits:
+ *   RSX_KEY_UNSIGNED  enc(x) = x
+ *   RSX_KEY_SIGNED    enc(x) = x ^ signbit                                (two's complement)
+ *   RSX_KEY_FLOAT     enc(x) = x ^ ((x >>arith (B-1)) | signbit)          (IEEE-754 binary32 for key_bytes 4, binary64 for 8)
+ * The float order is IEEE 754 totalOrder: -NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN.  The sorted keys are the input
+ * bit patterns, unchanged (no NaN canonicalisation).  This equals numpy's stable sort on any input without -0.0 and without NaNs
+ * whose sign bit is set; numpy and torch differ there: they treat -0.0 and +0.0 as equal (input order) and put every NaN last.
+ * With RSX_OPT_DESCENDING the passes sort ~enc(x).  Float keys and descending order are coded on the fly (the first pass of a
+ * sort encodes as it loads, the last one decodes as it stores; memory between the passes of a sort holds encoded keys, which is
+ * what RSX_OPT_FIRST_PASS / LAST_PASS ranges, rsx_sort_from_to and the step API see: their passes are digits of the ENCODED key).
+ * Engines of these kinds refuse rsx_partition*, rsx_key_range, rsx_sample_keys, rsx_msd_* and RSX_OPT_REF_DIAGNOSTICS. */
+#define RSX_KEY_UNSIGNED 0
+#define RSX_KEY_SIGNED 1
+#define RSX_KEY_FLOAT 2
+
 /* Options for rsx_set_option. */
 typedef enum rsx_option {
     RSX_OPT_PROFILE = 0,      /* HIP events around launches -> RuntimesGPU: 0 off, 1 every launch, 2 reorder only */
@@ -97,9 +112,12 @@ typedef enum rsx_option {
     RSX_OPT_XCD_PHASE = 13,   /* (default -1) with XCD_REMAP: XCD x enters its tile range x * value tiles in and wraps round, so that the eight
                                  XCDs do not walk ranges that start n/8 apart in lockstep (same HBM channels); -1 = an eighth of a
                                  range, 0 = lockstep.  Placement only: results are identical. */
-    RSX_OPT_LOOKAHEAD = 4     /* 1 (default): inside rsx_sort the reorder of pass p also counts pass p+1's digits per
+    RSX_OPT_LOOKAHEAD = 4,    /* 1 (default): inside rsx_sort the reorder of pass p also counts pass p+1's digits per
                                  output tile, so only the first pass runs the histogram kernel; 0: every pass runs
                                  histogram -> scan -> paste -> reorder separately.  Results are identical. */
+    RSX_OPT_DESCENDING = 21   /* 1: sort in descending order from the next sort on (0, default: ascending), for every key kind.  Still
+                                 STABLE: equal keys keep their input order (torch.sort(descending=True, stable=True)), which is not the
+                                 reverse of the ascending result.  The passes sort ~enc(x) ascending (see the key kinds above). */
 } rsx_option;
 
 /* Per-phase launch timings in milliseconds, the RuntimesGPU fields
@@ -145,11 +163,12 @@ const char* rsx_version(void);
  * + ComputeDeviceData's constructor: allocates inputKeys/outputKeys
  * (capacity*key_bytes each), inputPermutations/outputPermutations
  * (capacity*4 each, only with has_payload), the digit table and block sums.
- * key_bytes is 4 or 8; is_signed selects the OFFSET treatment of signed keys
- * (src/RadixSortGPU.cpp:436-440, RadixSort.cl:51,114).  The engine creates its
+ * key_bytes is 4 or 8; key_kind is RSX_KEY_UNSIGNED, RSX_KEY_SIGNED (the OFFSET treatment of signed keys,
+ * src/RadixSortGPU.cpp:436-440, RadixSort.cl:51,114) or RSX_KEY_FLOAT; any other value is refused with
+ * RSX_INITIALIZATION_FAILED.  The engine creates its
  * own stream; rsx_set_stream substitutes a caller-owned hipStream_t.
  * rsx_destroy replaces release() (src/RadixSortGPU.cpp:445-449). */
-int rsx_create(rsx_engine** out, int device, int key_bytes, int is_signed, int has_payload, uint64_t capacity);
+int rsx_create(rsx_engine** out, int device, int key_bytes, int key_kind, int has_payload, uint64_t capacity);
 int rsx_destroy(rsx_engine* e);
 int rsx_set_stream(rsx_engine* e, void* hip_stream);
 int rsx_get_stream(const rsx_engine* e, void** hip_stream);   /* the hipStream_t every call of this engine is enqueued on */
@@ -166,7 +185,9 @@ int rsx_resize(rsx_engine* e, uint64_t num_keys);
  *                host keys -> inputKeys, host perm -> inputPermutations (payload
  *                engines only; perm may be NULL otherwise).  Sets num_keys = n.
  * rsx_fill_pad = padGPUData (:270-285): fills inputKeys from byte_offset to the
- *                end of the active length with numeric_limits<T>::max()-1.
+ *                end of the active length with the key that sorts next-to-last: dec(all-ones - 1)
+ *                in the engine's encoding, i.e. numeric_limits<T>::max()-1 for integer keys in
+ *                ascending order.
  * rsx_download = CopyDataFromDevice + finish (:349-357,390-429): sorted keys,
  *                payload (NULL to skip), the first hist_cap entries of the digit
  *                table and the first globsum_cap block sums of the last pass. */

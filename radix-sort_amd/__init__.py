@@ -33,6 +33,9 @@ STATUS_NAMES = [
 # rsx_option (include/radixsort_hip.h)
 OPT_PROFILE, OPT_XCD_REMAP, OPT_FIRST_PASS, OPT_LAST_PASS, OPT_LOOKAHEAD, OPT_REF_DIAGNOSTICS, OPT_GRAPH, OPT_SMALL_SCAN, OPT_TILE_SORT, OPT_FUSED_SCAN = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 OPT_RADIX_BITS, OPT_SELF_SCAN, OPT_SMALL_TILE_MAX_KEYS, OPT_XCD_PHASE, OPT_SELF_SCAN_MAX_TILES, OPT_FUSED_SCAN_MAX_GROUPS = 10, 11, 12, 13, 14, 15
+OPT_DESCENDING = 21
+# key kinds of rsx_create (RSX_KEY_*): float keys sort in IEEE 754 totalOrder (-NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN)
+KEY_UNSIGNED, KEY_SIGNED, KEY_FLOAT = 0, 1, 2
 # rsx_experimental_option (include/radixsort_hip_experiments.h): known to the EXPERIMENTS build only (experiments()); the product library refuses them
 XOPT_DEBUG_RAISE_SCAN_TIMEOUT, XOPT_INLINE_SCAN, XOPT_INLINE_SCAN_MAX_GROUPS, XOPT_REORDER8_KERNEL, XOPT_REORDER8_STAY = 16, 17, 18, 19, 20
 EXPERIMENTS_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tools", "_variants", "libradixsort_hip_experiments.so")
@@ -213,25 +216,40 @@ def device_name(device: int = 0) -> str:
     return buf.value.decode()
 
 
-_KEY_DTYPES = {"uint32": (4, 0), "int32": (4, 1), "uint64": (8, 0), "int64": (8, 1)}
+# dtype name -> (key bytes, key kind)
+_KEY_DTYPES = {"uint32": (4, KEY_UNSIGNED), "int32": (4, KEY_SIGNED), "uint64": (8, KEY_UNSIGNED), "int64": (8, KEY_SIGNED),
+               "float32": (4, KEY_FLOAT), "float64": (8, KEY_FLOAT)}
 
 
 class Engine:
-    """One device + one stream + one buffer set: the C-ABI `rsx_engine`."""
+    """One device + one stream + one buffer set: the C-ABI `rsx_engine`.
 
-    def __init__(self, dtype, capacity: int, payload: bool = False, device: int = 0):
+    Float keys sort in IEEE 754 totalOrder, bit patterns unchanged: -0.0 before +0.0 and NaNs by sign and payload bits, where numpy
+    and torch treat ±0 as equal and put every NaN last.  descending=True sets OPT_DESCENDING: a stable descending sort (equal keys
+    keep their input order).  Float and descending engines refuse the partition, key-range, sampling and sharded-sort calls."""
+
+    def __init__(self, dtype, capacity: int, payload: bool = False, device: int = 0, descending: bool = False):
         self.lib = load_library()
         self.dtype = np.dtype(dtype)
         if self.dtype.name not in _KEY_DTYPES:
             raise TypeError(f"unsupported key type {self.dtype}")
-        kb, sg = _KEY_DTYPES[self.dtype.name]
+        kb, kind = _KEY_DTYPES[self.dtype.name]
+        self.key_kind = kind
+        self.descending = bool(descending)
         self.payload = bool(payload)
         self.capacity = int(capacity)
         self.device = int(device)
         self._h = C.c_void_p()
-        rc = self.lib.rsx_create(C.byref(self._h), device, kb, sg, int(self.payload), self.capacity)
+        rc = self.lib.rsx_create(C.byref(self._h), device, kb, kind, int(self.payload), self.capacity)
         if rc != 0:
             raise RadixSortError(rc, "rsx_create", self.lib.rsx_last_error().decode())
+        if self.descending:
+            self.set_option(OPT_DESCENDING, 1)
+
+    @property
+    def codec(self) -> bool:
+        """True for float keys and descending order: the engine sorts encoded keys and refuses the sharded-sort calls."""
+        return self.key_kind == KEY_FLOAT or self.descending
 
     # -- plumbing ----------------------------------------------------------
     def _check(self, rc: int, where: str) -> None:
@@ -265,6 +283,8 @@ class Engine:
 
     def set_option(self, option: int, value: int) -> None:
         self._check(self.lib.rsx_set_option(self._h, option, value), "rsx_set_option")
+        if option == OPT_DESCENDING:
+            self.descending = value != 0
 
     def geometry(self) -> Geometry:
         g = Geometry()
@@ -489,11 +509,11 @@ def tile_map(num_keys: int, tile_keys: int = 4096, xcd_remap: bool = True, xcd_p
     return out, ntiles.value
 
 
-def sort_host(keys: np.ndarray, payload: np.ndarray | None = None, device: int = 0):
+def sort_host(keys: np.ndarray, payload: np.ndarray | None = None, device: int = 0, descending: bool = False):
     """upload -> sort -> download of a host array (the shape of ExecuteTask,
-    reference src/CRadixSortTask.cpp:289-314).  Returns sorted keys (and payload)."""
+    reference src/CRadixSortTask.cpp:289-314).  Returns sorted keys (and payload).  Stable in both directions."""
     k = np.ascontiguousarray(keys)
-    with Engine(k.dtype, max(k.size, 1), payload=payload is not None, device=device) as e:
+    with Engine(k.dtype, max(k.size, 1), payload=payload is not None, device=device, descending=descending) as e:
         e.upload(k, payload)
         e.sort()
         if payload is None:

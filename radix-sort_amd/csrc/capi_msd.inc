@@ -31,6 +31,7 @@ int ensure_msd(rsx_engine* e)
 int rsx_msd_count(rsx_engine* e, const void* d_keys, uint64_t n, int bits, int world, uint64_t* d_counts)
 {
     if (!e || !d_counts) return fail(RSX_CALCULATION_FAILED, "rsx_msd_count: null argument");
+    if (e->codec()) return refuse_codec("rsx_msd_count");
     int rc = msd_check(e, bits, world, "rsx_msd_count");
     if (rc != RSX_OK) return rc;
     if (n > e->capacity) return fail(RSX_RESIZE_FAILED, "rsx_msd_count: beyond capacity");
@@ -87,6 +88,7 @@ int rsx_msd_count(rsx_engine* e, const void* d_keys, uint64_t n, int bits, int w
 int rsx_msd_scatter(rsx_engine* e, const void* d_keys, const uint32_t* d_payload, uint64_t n, void* d_staging, uint32_t* d_staging_payload)
 {
     if (!e) return fail(RSX_CALCULATION_FAILED, "rsx_msd_scatter: null engine");
+    if (e->codec()) return refuse_codec("rsx_msd_scatter");
     if (n == 0) {
         e->msd_keys = nullptr;
         e->msd_scattered = false;           // nothing was enqueued: a push has nothing to wait for (all its segments are empty)
@@ -126,6 +128,7 @@ int rsx_msd_plan(rsx_engine* e, const uint64_t* d_table, uint32_t stride, uint32
 {
     if (grouping != 0 && grouping != 1) return fail(RSX_CALCULATION_FAILED, "rsx_msd_plan: grouping is 0 (every wave aligned) or 1 (doubling groups)");
     if (!e || !d_table) return fail(RSX_CALCULATION_FAILED, "rsx_msd_plan: null argument");
+    if (e->codec()) return refuse_codec("rsx_msd_plan");
     if (e->msd_bits == 0) return fail(RSX_CALCULATION_FAILED, "rsx_msd_plan: must follow rsx_msd_count");
     const uint32_t nbuckets = 1u << e->msd_bits;
     if (rank < 0 || rank >= e->msd_world || stride < nbuckets || cap_at < nbuckets || cap_at + 3 > stride)
@@ -150,6 +153,7 @@ int rsx_msd_plan(rsx_engine* e, const uint64_t* d_table, uint32_t stride, uint32
 int rsx_msd_plan_wait(rsx_engine* e, uint64_t* wave_start, uint64_t* wave_count, uint64_t* loads, uint64_t* verdict)
 {
     if (!e) return fail(RSX_CALCULATION_FAILED, "rsx_msd_plan_wait: null engine");
+    if (e->codec()) return refuse_codec("rsx_msd_plan_wait");
     if (!e->msd_planned) return fail(RSX_CALCULATION_FAILED, "rsx_msd_plan_wait: must follow rsx_msd_plan");
     if (bind_device(e, RSX_CALCULATION_FAILED) != RSX_OK) return RSX_CALCULATION_FAILED;
     RSX_TRY(hipEventSynchronize(e->msd_event), RSX_CALCULATION_FAILED);
@@ -168,6 +172,7 @@ int rsx_msd_push(rsx_engine* e, int wave, const void* d_staging, const uint32_t*
                  void* hip_stream)
 {
     if (!e || !d_peer_keys) return fail(RSX_CALCULATION_FAILED, "rsx_msd_push: null argument");
+    if (e->codec()) return refuse_codec("rsx_msd_push");
     if (!e->msd_planned) return fail(RSX_CALCULATION_FAILED, "rsx_msd_push: must follow rsx_msd_plan");
     const int waves = (1 << e->msd_bits) / e->msd_world;
     if (wave < 0 || wave >= waves) return fail(RSX_CALCULATION_FAILED, "rsx_msd_push: wave out of range");

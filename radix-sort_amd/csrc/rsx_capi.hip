@@ -108,7 +108,10 @@ struct GraphEntry {      // one captured rsx_sort chain
 struct rsx_engine {
     int device = 0;
     int key_bytes = 4;
-    bool is_signed = false;
+    bool is_signed = false;                     // key_kind == RSX_KEY_SIGNED
+    int key_kind = RSX_KEY_UNSIGNED;            // RSX_KEY_UNSIGNED / SIGNED / FLOAT
+    bool descending = false;                    // RSX_OPT_DESCENDING
+    int codec_first = 0, codec_last = 0;        // pass range of the whole sort under way: its first pass encodes, its last one decodes
     bool has_payload = false;
     uint64_t capacity = 0;
     uint64_t n = 0;
@@ -257,6 +260,8 @@ struct rsx_engine {
     rsx_phase_stat stats[PH_COUNT];
 
     uint32_t passes() const { return static_cast<uint32_t>(key_bytes * 8 / RSX_RADIX_BITS); }
+    // float keys and descending order sort encoded keys (rsx::KeyCodec); such engines run every pass with flip = 0
+    bool codec() const { return key_kind == RSX_KEY_FLOAT || descending; }
     uint64_t ntiles(uint64_t count) const { return (count + kTileKeys - 1) / kTileKeys; }
 };
 
@@ -311,7 +316,70 @@ int drain_events(rsx_engine* e)
 template <typename Key>
 Key flip_mask(const rsx_engine* e)
 {
-    return e->is_signed ? static_cast<Key>(Key{1} << (sizeof(Key) * 8 - 1)) : Key{0};
+    return (e->is_signed && !e->codec()) ? static_cast<Key>(Key{1} << (sizeof(Key) * 8 - 1)) : Key{0};
+}
+
+// The engine's order map as codec constants (rsx_common.hpp): sort order = unsigned order of the encoded key.  Signed ascending
+// engines are (signbit, 0) here — the kernels fold that one into `flip` instead of coding keys.
+template <typename Key>
+void order_consts(const rsx_engine* e, Key* a, Key* m)
+{
+    constexpr Key sign = static_cast<Key>(Key{1} << (sizeof(Key) * 8 - 1));
+    if (e->key_kind == RSX_KEY_FLOAT) {
+        *m = static_cast<Key>(~sign);
+        *a = e->descending ? static_cast<Key>(~sign) : sign;
+    } else {
+        *m = Key{0};
+        const Key flip = e->is_signed ? sign : Key{0};
+        *a = e->descending ? static_cast<Key>(~flip) : flip;
+    }
+}
+
+// rsx::codec_decode on the host
+template <typename Key>
+Key codec_decode_host(Key y, Key a, Key m)
+{
+    const Key z = y ^ a;
+    const Key fill = (z >> (sizeof(Key) * 8 - 1)) ? static_cast<Key>(~Key{0}) : Key{0};
+    return z ^ (fill & m);
+}
+
+// codec bits of one launch: encode on load, decode on store
+constexpr int kEncode = 1, kDecode = 2;
+
+// The codec of one launch of a codec engine (zero constants for the direction it does not take).
+template <typename Key>
+rsx::KeyCodec<Key> key_codec(const rsx_engine* e, int cx)
+{
+    Key a = 0, m = 0;
+    order_consts<Key>(e, &a, &m);
+    rsx::KeyCodec<Key> c{};
+    if (cx & kEncode) {
+        c.ea = a;
+        c.em = m;
+    }
+    if (cx & kDecode) {
+        c.da = a;
+        c.dm = m;
+    }
+    return c;
+}
+
+// What the pass [pass, pass + width) of the sort [first, last) codes: the first pass encodes, the last one decodes.  0 on
+// engines without a codec: they take the plain kernels.
+int pass_codec(const rsx_engine* e, int pass, int width, int first, int last)
+{
+    if (!e->codec()) return 0;
+    return (pass == first ? kEncode : 0) | (pass + width == last ? kDecode : 0);
+}
+int pass_codec(const rsx_engine* e, int pass, int width)
+{
+    return pass_codec(e, pass, width, e->codec_first, e->codec_last);
+}
+
+int refuse_codec(const char* what)
+{
+    return fail(RSX_CALCULATION_FAILED, (std::string(what) + ": not available for float keys or descending order (the sharded sort and the partition passes take integer keys in ascending order)").c_str());
 }
 
 struct Grid {
@@ -344,7 +412,8 @@ rsx::SplitSet<Key> split_set(const rsx_engine* e, uint32_t nsplit)
 }
 
 template <typename Key, bool RANGED = false>
-int launch_histogram(rsx_engine* e, const void* in, uint64_t count, int shift, uint32_t mask, Key lo = Key{0}, Key mul = Key{0}, uint32_t nsplit = 0)
+int launch_histogram(rsx_engine* e, const void* in, uint64_t count, int shift, uint32_t mask, Key lo = Key{0}, Key mul = Key{0}, uint32_t nsplit = 0,
+                     int cx = 0)
 {
     if (count == 0) return RSX_OK;
     e->counted_keys = nullptr;          // e->table is about to be overwritten: an earlier rsx_partition_count* is void
@@ -352,9 +421,15 @@ int launch_histogram(rsx_engine* e, const void* in, uint64_t count, int shift, u
     e->globsum_valid = false;
     const Grid g = grid_for(e, count);
     Bracket b(e, PH_HISTO);
-    hipLaunchKernelGGL((rsx::histogram_kernel<Key, kTileThreads, kKeysPerThread, RANGED>), dim3(g.blocks), dim3(kTileThreads), 0, e->stream,
-                       static_cast<const Key*>(in), e->table, count, g.ntiles, g.tiles_per_xcd, g.remap, shift,
-                       flip_mask<Key>(e), mask, lo, mul, split_set<Key>(e, nsplit));
+    if (!RANGED && (cx & kEncode)) {
+        hipLaunchKernelGGL((rsx::histogram_kernel<Key, kTileThreads, kKeysPerThread, false, true>), dim3(g.blocks), dim3(kTileThreads), 0, e->stream,
+                           static_cast<const Key*>(in), e->table, count, g.ntiles, g.tiles_per_xcd, g.remap, shift,
+                           flip_mask<Key>(e), mask, lo, mul, split_set<Key>(e, nsplit), nullptr, nullptr, nullptr, key_codec<Key>(e, kEncode));
+    } else {
+        hipLaunchKernelGGL((rsx::histogram_kernel<Key, kTileThreads, kKeysPerThread, RANGED>), dim3(g.blocks), dim3(kTileThreads), 0, e->stream,
+                           static_cast<const Key*>(in), e->table, count, g.ntiles, g.tiles_per_xcd, g.remap, shift,
+                           flip_mask<Key>(e), mask, lo, mul, split_set<Key>(e, nsplit));
+    }
     RSX_TRY(hipGetLastError(), RSX_CALCULATION_FAILED);
     return RSX_OK;
 }
@@ -472,15 +547,28 @@ int launch_paste(rsx_engine* e, uint64_t count)
 template <typename Key, bool PAYLOAD, bool LOOKAHEAD, bool RANGED = false, int KPT = kKeysPerThread, int THREADS = kTileThreads>
 int launch_reorder_t(rsx_engine* e, const void* in, void* out, const uint32_t* pin, uint32_t* pout, uint64_t count, int shift,
                      uint32_t mask, int next_shift, Key lo = Key{0}, Key mul = Key{0}, uint32_t nsplit = 0,
-                     rsx::SelfScanArgs self = rsx::SelfScanArgs{nullptr, nullptr, nullptr}, uint32_t* next_counts = nullptr)
+                     rsx::SelfScanArgs self = rsx::SelfScanArgs{nullptr, nullptr, nullptr}, uint32_t* next_counts = nullptr, int cx = 0)
 {
     using L = rsx::ReorderLayout<Key, THREADS, KPT>;
     const Grid g = grid_for(e, count, THREADS * KPT);
     e->last_in = in;
     e->last_shift = shift;
     Bracket b(e, PH_REORDER);
+    const size_t lds = L::BYTES + (KPT != kKeysPerThread ? 0u : e->reorder_extra_lds >= 0 ? static_cast<size_t>(e->reorder_extra_lds) : (PAYLOAD && sizeof(Key) == 4 && !RANGED) ? (16u << 10) : 0u);
+    if constexpr (!RANGED) {
+        if (cx) {
+            // first / last pass of a float or descending sort (rsx::KeyCodec)
+            hipLaunchKernelGGL((rsx::reorder_kernel<Key, THREADS, KPT, PAYLOAD, LOOKAHEAD, false, false, true>), dim3(g.blocks), dim3(THREADS), lds,
+                               e->stream, static_cast<const Key*>(in), static_cast<Key*>(out), pin, pout, e->table, count,
+                               g.ntiles, g.tiles_per_xcd, g.remap, shift, flip_mask<Key>(e), mask,
+                               next_counts ? next_counts : e->counts_next, next_shift, static_cast<const uint32_t*>(nullptr),
+                               lo, mul, split_set<Key>(e, nsplit), self, rsx::InlineScanArgs{}, key_codec<Key>(e, cx));
+            RSX_TRY(hipGetLastError(), RSX_CALCULATION_FAILED);
+            return RSX_OK;
+        }
+    }
     hipLaunchKernelGGL((rsx::reorder_kernel<Key, THREADS, KPT, PAYLOAD, LOOKAHEAD, RANGED>), dim3(g.blocks), dim3(THREADS),
-                       L::BYTES + (KPT != kKeysPerThread ? 0u : e->reorder_extra_lds >= 0 ? static_cast<size_t>(e->reorder_extra_lds) : (PAYLOAD && sizeof(Key) == 4 && !RANGED) ? (16u << 10) : 0u),
+                       lds,
                        e->stream, static_cast<const Key*>(in), static_cast<Key*>(out), pin, pout, e->table, count,
                        g.ntiles, g.tiles_per_xcd, g.remap, shift, flip_mask<Key>(e), mask,
                        next_counts ? next_counts : e->counts_next, next_shift,
@@ -496,8 +584,9 @@ int launch_reorder_t(rsx_engine* e, const void* in, void* out, const uint32_t* p
 
 template <typename Key>
 int launch_reorder(rsx_engine* e, const void* in, void* out, const uint32_t* pin, uint32_t* pout, uint64_t count, int shift,
-                   uint32_t mask, int next_shift = -1)
+                   uint32_t mask, int next_shift = -1, int cx = 0)
 {
+    const rsx::SelfScanArgs none{nullptr, nullptr, nullptr};
     if (count == 0) return RSX_OK;
     const bool payload = pin && pout;
 #if RSX_PRODUCT_SHAPE
@@ -505,17 +594,17 @@ int launch_reorder(rsx_engine* e, const void* in, void* out, const uint32_t* pin
         // 64-bit keys WITH payload: the same 4096-key tiles (same table) ranked by 512 threads x 8 keys — 140 VGPRs and three waves per SIMD become ~90 and four;
         // 1.149-1.184 -> 1.092-1.127 ms per launch (profiles/r03_ab_4bit_512x8.txt).  Every other 4-bit variant is 1-4 % slower that way and keeps 256 x 16.
         if (payload && (e->reorder_wide >= 0 ? e->reorder_wide != 0 : true)) {
-            return next_shift >= 0 ? launch_reorder_t<Key, true, true, false, 8, 512>(e, in, out, pin, pout, count, shift, mask, next_shift)
-                                   : launch_reorder_t<Key, true, false, false, 8, 512>(e, in, out, pin, pout, count, shift, mask, 0);
+            return next_shift >= 0 ? launch_reorder_t<Key, true, true, false, 8, 512>(e, in, out, pin, pout, count, shift, mask, next_shift, Key{0}, Key{0}, 0, none, nullptr, cx)
+                                   : launch_reorder_t<Key, true, false, false, 8, 512>(e, in, out, pin, pout, count, shift, mask, 0, Key{0}, Key{0}, 0, none, nullptr, cx);
         }
     }
 #endif
     if (next_shift >= 0) {
-        return payload ? launch_reorder_t<Key, true, true>(e, in, out, pin, pout, count, shift, mask, next_shift)
-                       : launch_reorder_t<Key, false, true>(e, in, out, nullptr, nullptr, count, shift, mask, next_shift);
+        return payload ? launch_reorder_t<Key, true, true>(e, in, out, pin, pout, count, shift, mask, next_shift, Key{0}, Key{0}, 0, none, nullptr, cx)
+                       : launch_reorder_t<Key, false, true>(e, in, out, nullptr, nullptr, count, shift, mask, next_shift, Key{0}, Key{0}, 0, none, nullptr, cx);
     }
-    return payload ? launch_reorder_t<Key, true, false>(e, in, out, pin, pout, count, shift, mask, 0)
-                   : launch_reorder_t<Key, false, false>(e, in, out, nullptr, nullptr, count, shift, mask, 0);
+    return payload ? launch_reorder_t<Key, true, false>(e, in, out, pin, pout, count, shift, mask, 0, Key{0}, Key{0}, 0, none, nullptr, cx)
+                   : launch_reorder_t<Key, false, false>(e, in, out, nullptr, nullptr, count, shift, mask, 0, Key{0}, Key{0}, 0, none, nullptr, cx);
 }
 
 // The scatter kernels address their staging image from LDS address 0 (rsx::lds_store_at): true when the kernel declares no static LDS
@@ -542,24 +631,24 @@ int lds_base_probe(rsx_engine* e)
     return RSX_OK;
 }
 
-template <typename Key, bool PAYLOAD, bool LOOKAHEAD, bool RANGED = false, int KPT = kKeysPerThread, int THREADS = kTileThreads>
+template <typename Key, bool PAYLOAD, bool LOOKAHEAD, bool RANGED = false, int KPT = kKeysPerThread, int THREADS = kTileThreads, bool CODEC = false>
 int allow_lds()
 {
     using L = rsx::ReorderLayout<Key, THREADS, KPT>;
-    const void* fn = reinterpret_cast<const void*>(&rsx::reorder_kernel<Key, THREADS, KPT, PAYLOAD, LOOKAHEAD, RANGED>);
+    const void* fn = reinterpret_cast<const void*>(&rsx::reorder_kernel<Key, THREADS, KPT, PAYLOAD, LOOKAHEAD, RANGED, false, CODEC>);
     RSX_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(L::BYTES) + (64 << 10)), RSX_INITIALIZATION_FAILED);
     return no_static_lds(fn, "reorder_kernel");
 }
 
 // One full pass chain on explicit buffers: histogram -> scan -> paste -> reorder.
 template <typename Key>
-int run_pass(rsx_engine* e, const void* in, void* out, const uint32_t* pin, uint32_t* pout, uint64_t count, int shift, uint32_t mask)
+int run_pass(rsx_engine* e, const void* in, void* out, const uint32_t* pin, uint32_t* pout, uint64_t count, int shift, uint32_t mask, int cx = 0)
 {
     int rc;
-    if ((rc = launch_histogram<Key>(e, in, count, shift, mask)) != RSX_OK) return rc;
+    if ((rc = launch_histogram<Key>(e, in, count, shift, mask, Key{0}, Key{0}, 0, cx)) != RSX_OK) return rc;
     if ((rc = launch_scan(e, count)) != RSX_OK) return rc;
     if ((rc = launch_paste(e, count)) != RSX_OK) return rc;
-    return launch_reorder<Key>(e, in, out, pin, pout, count, shift, mask);
+    return launch_reorder<Key>(e, in, out, pin, pout, count, shift, mask, -1, cx);
 }
 
 // One stable pass with the ranged bucket function (multi-GPU partition).
@@ -605,9 +694,17 @@ int launch_tile_sort_t(rsx_engine* e, const void* in, void* out, void* before_la
 {
     using L = rsx::TileSortLayout<Key, kTileThreads, kKeysPerThread>;
     Bracket b(e, PH_REORDER);
-    hipLaunchKernelGGL((rsx::tile_sort_kernel<Key, kTileThreads, kKeysPerThread, PAYLOAD>), dim3(1), dim3(kTileThreads), L::BYTES, e->stream,
-                       static_cast<const Key*>(in), static_cast<Key*>(out), static_cast<Key*>(before_last), pin, pout, pbefore_last,
-                       static_cast<uint32_t>(count), e->first_pass, e->last_pass, flip_mask<Key>(e), e->table, e->globsum, e->temp);
+    if (e->codec()) {
+        // (the one-workgroup sort runs the whole range: it encodes on load and decodes on store)
+        hipLaunchKernelGGL((rsx::tile_sort_kernel<Key, kTileThreads, kKeysPerThread, PAYLOAD, true>), dim3(1), dim3(kTileThreads), L::BYTES, e->stream,
+                           static_cast<const Key*>(in), static_cast<Key*>(out), static_cast<Key*>(before_last), pin, pout, pbefore_last,
+                           static_cast<uint32_t>(count), e->first_pass, e->last_pass, flip_mask<Key>(e), e->table, e->globsum, e->temp,
+                           key_codec<Key>(e, pass_codec(e, e->first_pass, e->last_pass - e->first_pass)));
+    } else {
+        hipLaunchKernelGGL((rsx::tile_sort_kernel<Key, kTileThreads, kKeysPerThread, PAYLOAD>), dim3(1), dim3(kTileThreads), L::BYTES, e->stream,
+                           static_cast<const Key*>(in), static_cast<Key*>(out), static_cast<Key*>(before_last), pin, pout, pbefore_last,
+                           static_cast<uint32_t>(count), e->first_pass, e->last_pass, flip_mask<Key>(e), e->table, e->globsum, e->temp);
+    }
     RSX_TRY(hipGetLastError(), RSX_CALCULATION_FAILED);
     return RSX_OK;
 }
@@ -665,9 +762,16 @@ int sort_selfscan_enqueue(rsx_engine* e, const void* ext_keys, const uint32_t* e
     e->counted_keys = nullptr;
     {
         Bracket b(e, PH_HISTO);
-        hipLaunchKernelGGL((rsx::histogram_kernel<Key, kTileThreads, KPT, false>), dim3(g.blocks), dim3(kTileThreads), 0, e->stream,
-                           static_cast<const Key*>(in), e->table, count, g.ntiles, g.tiles_per_xcd, g.remap, e->first_pass * RSX_RADIX_BITS,
-                           flip_mask<Key>(e), static_cast<uint32_t>(RSX_RADIX - 1), Key{0}, Key{0}, split_set<Key>(e, 0), e->cnt3[0], e->cnt3[1], e->cnt3[2]);
+        if (pass_codec(e, e->first_pass, 1) & kEncode) {
+            hipLaunchKernelGGL((rsx::histogram_kernel<Key, kTileThreads, KPT, false, true>), dim3(g.blocks), dim3(kTileThreads), 0, e->stream,
+                               static_cast<const Key*>(in), e->table, count, g.ntiles, g.tiles_per_xcd, g.remap, e->first_pass * RSX_RADIX_BITS,
+                               flip_mask<Key>(e), static_cast<uint32_t>(RSX_RADIX - 1), Key{0}, Key{0}, split_set<Key>(e, 0), e->cnt3[0], e->cnt3[1], e->cnt3[2],
+                               key_codec<Key>(e, kEncode));
+        } else {
+            hipLaunchKernelGGL((rsx::histogram_kernel<Key, kTileThreads, KPT, false>), dim3(g.blocks), dim3(kTileThreads), 0, e->stream,
+                               static_cast<const Key*>(in), e->table, count, g.ntiles, g.tiles_per_xcd, g.remap, e->first_pass * RSX_RADIX_BITS,
+                               flip_mask<Key>(e), static_cast<uint32_t>(RSX_RADIX - 1), Key{0}, Key{0}, split_set<Key>(e, 0), e->cnt3[0], e->cnt3[1], e->cnt3[2]);
+        }
         RSX_TRY(hipGetLastError(), RSX_CALCULATION_FAILED);
     }
     int i = 0;
@@ -679,13 +783,14 @@ int sort_selfscan_enqueue(rsx_engine* e, const void* ext_keys, const uint32_t* e
         const int shift = pass * RSX_RADIX_BITS;
         const rsx::SelfScanArgs self{e->cnt3[i % 3], e->cnt3[(i + 2) % 3], (last && KPT == kKeysPerThread) ? e->table : nullptr};
         uint32_t* next = e->cnt3[(i + 1) % 3];
+        const int cx = pass_codec(e, pass, 1);
         int rc;
         if (e->has_payload) {
-            rc = last ? launch_reorder_t<Key, true, false, false, KPT>(e, in, out, pin, pout, count, shift, RSX_RADIX - 1, 0, Key{0}, Key{0}, 0, self, next)
-                      : launch_reorder_t<Key, true, true, false, KPT>(e, in, out, pin, pout, count, shift, RSX_RADIX - 1, shift + RSX_RADIX_BITS, Key{0}, Key{0}, 0, self, next);
+            rc = last ? launch_reorder_t<Key, true, false, false, KPT>(e, in, out, pin, pout, count, shift, RSX_RADIX - 1, 0, Key{0}, Key{0}, 0, self, next, cx)
+                      : launch_reorder_t<Key, true, true, false, KPT>(e, in, out, pin, pout, count, shift, RSX_RADIX - 1, shift + RSX_RADIX_BITS, Key{0}, Key{0}, 0, self, next, cx);
         } else {
-            rc = last ? launch_reorder_t<Key, false, false, false, KPT>(e, in, out, nullptr, nullptr, count, shift, RSX_RADIX - 1, 0, Key{0}, Key{0}, 0, self, next)
-                      : launch_reorder_t<Key, false, true, false, KPT>(e, in, out, nullptr, nullptr, count, shift, RSX_RADIX - 1, shift + RSX_RADIX_BITS, Key{0}, Key{0}, 0, self, next);
+            rc = last ? launch_reorder_t<Key, false, false, false, KPT>(e, in, out, nullptr, nullptr, count, shift, RSX_RADIX - 1, 0, Key{0}, Key{0}, 0, self, next, cx)
+                      : launch_reorder_t<Key, false, true, false, KPT>(e, in, out, nullptr, nullptr, count, shift, RSX_RADIX - 1, shift + RSX_RADIX_BITS, Key{0}, Key{0}, 0, self, next, cx);
         }
         if (rc != RSX_OK) return rc;
         in = out;
@@ -732,11 +837,11 @@ bool r8_wide_for(const rsx_engine* e, bool key64, bool has_payload)
     return key64 && !has_payload;
 }
 
-template <typename K, int THREADS, int KPT, bool PAYLOAD, bool PACKED32 = false>
+template <typename K, int THREADS, int KPT, bool PAYLOAD, bool PACKED32 = false, bool CODEC = false>
 int allow_lds8(int extra)
 {
     using L = rsx::Reorder8Layout<K, THREADS, KPT, PAYLOAD>;
-    const void* fn = reinterpret_cast<const void*>(&rsx::reorder8_kernel<K, THREADS, KPT, PAYLOAD, PACKED32>);
+    const void* fn = reinterpret_cast<const void*>(&rsx::reorder8_kernel<K, THREADS, KPT, PAYLOAD, PACKED32, CODEC>);
     RSX_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(L::BYTES) + extra), RSX_INITIALIZATION_FAILED);
     return no_static_lds(fn, "reorder8_kernel");
 }
@@ -770,6 +875,16 @@ int ensure_radix8(rsx_engine* e)
         if (rc == RSX_OK) rc = allow_lds8<uint64_t, kTileThreads, kKeysPerThread, false, true>(extra);
         if (rc == RSX_OK) rc = allow_lds8<uint64_t, 512, 8, false, true>(extra);
     }
+    if (e->codec()) {                          // the first and last pass of a float / descending sort
+        if (rc == RSX_OK) rc = allow_lds8<Key, kTileThreads, kKeysPerThread, false, false, true>(extra);
+        if (rc == RSX_OK) rc = allow_lds8<Key, kTileThreads, kKeysPerThread, true, false, true>(extra);
+        if (rc == RSX_OK) rc = allow_lds8<Key, 512, 8, false, false, true>(extra);
+        if (rc == RSX_OK) rc = allow_lds8<Key, 512, 8, true, false, true>(extra);
+        if constexpr (sizeof(Key) == 4) {
+            if (rc == RSX_OK) rc = allow_lds8<uint64_t, kTileThreads, kKeysPerThread, false, true, true>(extra);
+            if (rc == RSX_OK) rc = allow_lds8<uint64_t, 512, 8, false, true, true>(extra);
+        }
+    }
 #ifdef RSX_EXPERIMENTS
     if (rc == RSX_OK) rc = ensure_radix8_experiments<Key>(e, extra);
 #endif
@@ -778,10 +893,28 @@ int ensure_radix8(rsx_engine* e)
     return RSX_OK;
 }
 
+// One reorder8 launch, plain or with the codec of the first / last pass of a float or descending sort (cx, rsx::Codec8).
+template <typename K, int THREADS, int KPT, bool PAYLOAD, bool PACKED32 = false>
+void launch_reorder8_v(rsx_engine* e, const dim3& grid, size_t lds, const void* in, void* out, const uint32_t* pin, uint32_t* pout, uint64_t count,
+                       const Grid& g, uint32_t chunk_groups, int shift, K flip, int cx)
+{
+    using CK = typename std::conditional<PACKED32, uint32_t, K>::type;
+    if (cx) {
+        hipLaunchKernelGGL((rsx::reorder8_kernel<K, THREADS, KPT, PAYLOAD, PACKED32, true>), grid, dim3(THREADS), lds, e->stream,
+                           static_cast<const K*>(in), static_cast<K*>(out), pin, pout, e->table8, e->gsum8, e->cbase8, chunk_groups,
+                           count, g.ntiles, g.tiles_per_xcd, g.remap, shift, flip, key_codec<CK>(e, cx));
+    } else {
+        hipLaunchKernelGGL((rsx::reorder8_kernel<K, THREADS, KPT, PAYLOAD, PACKED32>), grid, dim3(THREADS), lds, e->stream,
+                           static_cast<const K*>(in), static_cast<K*>(out), pin, pout, e->table8, e->gsum8, e->cbase8, chunk_groups,
+                           count, g.ntiles, g.tiles_per_xcd, g.remap, shift, flip);
+    }
+}
+
 // One scatter launch of an 8-bit pass: by variant (keys only / separate payload array / uint32 key + payload packed into one 64-bit
 // element) on 256 x 16 or 512 x 8 threads x keys; the same 4096-key tiles and tables for all of them.
 template <typename Key>
-int launch_reorder8(rsx_engine* e, const void* in, void* out, const uint32_t* pin, uint32_t* pout, uint64_t count, const Grid& g, uint32_t chunk_groups, int shift)
+int launch_reorder8(rsx_engine* e, const void* in, void* out, const uint32_t* pin, uint32_t* pout, uint64_t count, const Grid& g, uint32_t chunk_groups, int shift,
+                    int cx = 0)
 {
     const Key flip = flip_mask<Key>(e);
     e->last_in = nullptr;            // an 8-bit pass has no counterpart in the reference's geometry: RSX_OPT_REF_DIAGNOSTICS refuses after it (a later 4-bit pass sets it again)
@@ -789,43 +922,31 @@ int launch_reorder8(rsx_engine* e, const void* in, void* out, const uint32_t* pi
     const bool wide = r8_wide_for(e, sizeof(Key) == 8, e->has_payload);
     const size_t wide_extra = e->r8_extra_lds >= 0 ? static_cast<size_t>(e->r8_extra_lds) : 0;      // (57-62 KiB per workgroup: two per CU as they stand)
     const dim3 grid(g.blocks);
-    // (dynamic LDS per variant, named here: template commas do not survive inside the launch macro)
     constexpr size_t lds_packed = rsx::Reorder8Layout<uint64_t, kTileThreads, kKeysPerThread>::BYTES, lds_packed_wide = rsx::Reorder8Layout<uint64_t, 512, 8, false>::BYTES;
     constexpr size_t lds_pay = rsx::Reorder8Layout<Key, kTileThreads, kKeysPerThread, true>::BYTES, lds_pay_wide = rsx::Reorder8Layout<Key, 512, 8, true>::BYTES;
     constexpr size_t lds_keys = rsx::Reorder8Layout<Key, kTileThreads, kKeysPerThread>::BYTES, lds_keys_wide = rsx::Reorder8Layout<Key, 512, 8, false>::BYTES;
     if (packed) {
         // uint32 key + payload as one 64-bit element (rsx::reorder8_kernel<.., PACKED32>)
         if (wide) {
-            hipLaunchKernelGGL((rsx::reorder8_kernel<uint64_t, 512, 8, false, true>), grid, dim3(512), lds_packed_wide + wide_extra, e->stream,
-                               static_cast<const uint64_t*>(in), static_cast<uint64_t*>(out), pin, pout, e->table8, e->gsum8, e->cbase8, chunk_groups,
-                               count, g.ntiles, g.tiles_per_xcd, g.remap, shift, static_cast<uint64_t>(flip));
+            launch_reorder8_v<uint64_t, 512, 8, false, true>(e, grid, lds_packed_wide + wide_extra, in, out, pin, pout, count, g, chunk_groups, shift,
+                                                             static_cast<uint64_t>(flip), cx);
         } else {
-            hipLaunchKernelGGL((rsx::reorder8_kernel<uint64_t, kTileThreads, kKeysPerThread, false, true>), grid, dim3(kTileThreads),
-                               lds_packed + r8_extra_lds_for(e, true, false), e->stream,
-                               static_cast<const uint64_t*>(in), static_cast<uint64_t*>(out), pin, pout, e->table8, e->gsum8, e->cbase8, chunk_groups,
-                               count, g.ntiles, g.tiles_per_xcd, g.remap, shift, static_cast<uint64_t>(flip));
+            launch_reorder8_v<uint64_t, kTileThreads, kKeysPerThread, false, true>(e, grid, lds_packed + r8_extra_lds_for(e, true, false), in, out, pin, pout, count, g,
+                                                                                   chunk_groups, shift, static_cast<uint64_t>(flip), cx);
         }
     } else if (e->has_payload) {
         if (wide) {
-            hipLaunchKernelGGL((rsx::reorder8_kernel<Key, 512, 8, true>), grid, dim3(512), lds_pay_wide + wide_extra, e->stream,
-                               static_cast<const Key*>(in), static_cast<Key*>(out), pin, pout, e->table8, e->gsum8, e->cbase8, chunk_groups,
-                               count, g.ntiles, g.tiles_per_xcd, g.remap, shift, flip);
+            launch_reorder8_v<Key, 512, 8, true>(e, grid, lds_pay_wide + wide_extra, in, out, pin, pout, count, g, chunk_groups, shift, flip, cx);
         } else {
-            hipLaunchKernelGGL((rsx::reorder8_kernel<Key, kTileThreads, kKeysPerThread, true>), grid, dim3(kTileThreads),
-                               lds_pay + r8_extra_lds_for(e, sizeof(Key) == 8, true), e->stream,
-                               static_cast<const Key*>(in), static_cast<Key*>(out), pin, pout, e->table8, e->gsum8, e->cbase8, chunk_groups,
-                               count, g.ntiles, g.tiles_per_xcd, g.remap, shift, flip);
+            launch_reorder8_v<Key, kTileThreads, kKeysPerThread, true>(e, grid, lds_pay + r8_extra_lds_for(e, sizeof(Key) == 8, true), in, out, pin, pout, count, g,
+                                                                      chunk_groups, shift, flip, cx);
         }
     } else {
         if (wide) {
-            hipLaunchKernelGGL((rsx::reorder8_kernel<Key, 512, 8, false>), grid, dim3(512), lds_keys_wide + wide_extra, e->stream,
-                               static_cast<const Key*>(in), static_cast<Key*>(out), nullptr, nullptr, e->table8, e->gsum8, e->cbase8, chunk_groups,
-                               count, g.ntiles, g.tiles_per_xcd, g.remap, shift, flip);
+            launch_reorder8_v<Key, 512, 8, false>(e, grid, lds_keys_wide + wide_extra, in, out, nullptr, nullptr, count, g, chunk_groups, shift, flip, cx);
         } else {
-            hipLaunchKernelGGL((rsx::reorder8_kernel<Key, kTileThreads, kKeysPerThread, false>), grid, dim3(kTileThreads),
-                               lds_keys + r8_extra_lds_for(e, sizeof(Key) == 8, false), e->stream,
-                               static_cast<const Key*>(in), static_cast<Key*>(out), nullptr, nullptr, e->table8, e->gsum8, e->cbase8, chunk_groups,
-                               count, g.ntiles, g.tiles_per_xcd, g.remap, shift, flip);
+            launch_reorder8_v<Key, kTileThreads, kKeysPerThread, false>(e, grid, lds_keys + r8_extra_lds_for(e, sizeof(Key) == 8, false), in, out, nullptr, nullptr,
+                                                                       count, g, chunk_groups, shift, flip, cx);
         }
     }
     RSX_TRY(hipGetLastError(), RSX_CALCULATION_FAILED);
@@ -847,13 +968,18 @@ Scan8Shape scan8_shape(uint32_t ntiles)
 
 // histogram8 -> scan8 (blocks, chunks[, top]) of one 8-bit pass: leaves table8 / gsum8 / cbase8 ready for the scatter
 template <typename Key>
-int launch_count8(rsx_engine* e, const void* in, uint64_t count, const Grid& g, const Scan8Shape& s, int shift)
+int launch_count8(rsx_engine* e, const void* in, uint64_t count, const Grid& g, const Scan8Shape& s, int shift, int cx = 0)
 {
     e->msd_keys = nullptr;              // the 8-bit tables are about to be overwritten: a pending rsx_msd_count is void
     {
         Bracket b(e, PH_HISTO);
-        hipLaunchKernelGGL((rsx::histogram8_kernel<Key, kTileThreads, kKeysPerThread>), dim3(g.blocks), dim3(kTileThreads), 0, e->stream,
-                           static_cast<const Key*>(in), e->counts8, count, g.ntiles, g.tiles_per_xcd, g.remap, shift, flip_mask<Key>(e));
+        if (cx & kEncode) {
+            hipLaunchKernelGGL((rsx::histogram8_kernel<Key, kTileThreads, kKeysPerThread, true>), dim3(g.blocks), dim3(kTileThreads), 0, e->stream,
+                               static_cast<const Key*>(in), e->counts8, count, g.ntiles, g.tiles_per_xcd, g.remap, shift, flip_mask<Key>(e), key_codec<Key>(e, kEncode));
+        } else {
+            hipLaunchKernelGGL((rsx::histogram8_kernel<Key, kTileThreads, kKeysPerThread>), dim3(g.blocks), dim3(kTileThreads), 0, e->stream,
+                               static_cast<const Key*>(in), e->counts8, count, g.ntiles, g.tiles_per_xcd, g.remap, shift, flip_mask<Key>(e));
+        }
     }
     {
         Bracket b(e, PH_SCAN);
@@ -891,14 +1017,15 @@ int sort8_chain_enqueue(rsx_engine* e, const void* ext_keys, const uint32_t* ext
         void* out = to_caller ? e->final_keys_out : e->keys[dst];
         uint32_t* pout = e->has_payload ? (to_caller ? e->final_perm_out : e->perm[dst]) : nullptr;
         const int shift = pass * RSX_RADIX_BITS;
-        int rc = launch_count8<Key>(e, in, count, g, s, shift);
+        const int cx = pass_codec(e, pass, 2);      // (the mixed chain's 8-bit part ends before the sort does: it encodes, never decodes)
+        int rc = launch_count8<Key>(e, in, count, g, s, shift, cx);
         if (rc != RSX_OK) return rc;
         {
             Bracket b(e, PH_REORDER);
 #ifdef RSX_EXPERIMENTS
-            if (!launch_reorder8_experiment<Key>(e, in, out, pin, pout, count, g, s.chunk_groups, shift, pass / 2, pass == e->first_pass, &rc))
+            if (e->codec() || !launch_reorder8_experiment<Key>(e, in, out, pin, pout, count, g, s.chunk_groups, shift, pass / 2, pass == e->first_pass, &rc))
 #endif
-                rc = launch_reorder8<Key>(e, in, out, pin, pout, count, g, s.chunk_groups, shift);
+                rc = launch_reorder8<Key>(e, in, out, pin, pout, count, g, s.chunk_groups, shift, cx);
         }
         if (rc != RSX_OK) return rc;
         in = out;                                     // (launch_reorder8 cleared last_in: the reference-geometry diagnostics describe 4-bit passes, rsx_download refuses them after this chain)
@@ -927,7 +1054,20 @@ bool inline_scan_takes(const rsx_engine* e, uint64_t count);
 #endif
 
 template <typename Key>
+int sort_chain_passes(rsx_engine* e, const void* ext_keys, const uint32_t* ext_perm, uint64_t count);
+
+// The sort of passes [first_pass, last_pass): its first pass encodes and its last one decodes the keys of a codec engine,
+// whichever chain (or chains: the mixed one) runs them.
+template <typename Key>
 int sort_chain_enqueue(rsx_engine* e, const void* ext_keys, const uint32_t* ext_perm, uint64_t count)
+{
+    e->codec_first = e->first_pass;
+    e->codec_last = e->last_pass;
+    return sort_chain_passes<Key>(e, ext_keys, ext_perm, count);
+}
+
+template <typename Key>
+int sort_chain_passes(rsx_engine* e, const void* ext_keys, const uint32_t* ext_perm, uint64_t count)
 {
     // (8-bit digits pay off from 2^19 keys: below that the 4-bit self-scan chain — 9 launches of a 1024- or 4096-key tile's
     // latency — is faster than 4 passes of four launches; same result either way)
@@ -950,7 +1090,7 @@ int sort_chain_enqueue(rsx_engine* e, const void* ext_keys, const uint32_t* ext_
         e->final_perm_out = perm_out;
         if (rc != RSX_OK) return rc;
         e->first_pass = last - 1;
-        rc = sort_chain_enqueue<Key>(e, nullptr, nullptr, count);
+        rc = sort_chain_passes<Key>(e, nullptr, nullptr, count);
         e->first_pass = first;
         return rc;
     }
@@ -965,7 +1105,7 @@ int sort_chain_enqueue(rsx_engine* e, const void* ext_keys, const uint32_t* ext_
         return sort_selfscan_enqueue<Key>(e, ext_keys, ext_perm, count);
     }
 #if defined(RSX_EXPERIMENTS) && RSX_PRODUCT_SHAPE
-    if (inline_scan_takes(e, count)) return sort_inline_enqueue<Key>(e, ext_keys, ext_perm, count);
+    if (!e->codec() && inline_scan_takes(e, count)) return sort_inline_enqueue<Key>(e, ext_keys, ext_perm, count);
 #endif
     // Ping-pong.  With external input the first pass reads the caller's buffer (never
     // written) and the chain continues inside the engine's two buffers.
@@ -982,14 +1122,15 @@ int sort_chain_enqueue(rsx_engine* e, const void* ext_keys, const uint32_t* ext_
         void* out = to_caller ? e->final_keys_out : e->keys[dst];
         uint32_t* pout = e->has_payload ? (to_caller ? e->final_perm_out : e->perm[dst]) : nullptr;
         const int shift = pass * RSX_RADIX_BITS;
+        const int cx = pass_codec(e, pass, 1);
         int rc;
         if (!e->lookahead) {
-            rc = run_pass<Key>(e, in, out, pin, pout, count, shift, RSX_RADIX - 1);
+            rc = run_pass<Key>(e, in, out, pin, pout, count, shift, RSX_RADIX - 1, cx);
         } else {
             // only the first pass reads the keys for a histogram; every later table was
             // counted by the previous pass's reorder while it scattered (look-ahead)
             const bool first = pass == e->first_pass;
-            rc = first ? launch_histogram<Key>(e, in, count, shift, RSX_RADIX - 1) : RSX_OK;
+            rc = first ? launch_histogram<Key>(e, in, count, shift, RSX_RADIX - 1, Key{0}, Key{0}, 0, cx) : RSX_OK;
             bool pasted = false;
             if (rc == RSX_OK) pasted = launch_scan_small(e, count, /*from_counts=*/!first, &rc);
             if (rc == RSX_OK && !pasted) pasted = launch_scan_fused(e, count, /*from_counts=*/!first, &rc);
@@ -999,7 +1140,7 @@ int sort_chain_enqueue(rsx_engine* e, const void* ext_keys, const uint32_t* ext_
             const bool last = pass + 1 == e->last_pass;
             if (rc == RSX_OK && !pasted) rc = merged ? launch_paste_scan(e, count) : launch_paste(e, count);
             const int next_shift = last ? -1 : shift + RSX_RADIX_BITS;
-            if (rc == RSX_OK) rc = launch_reorder<Key>(e, in, out, pin, pout, count, shift, RSX_RADIX - 1, next_shift);
+            if (rc == RSX_OK) rc = launch_reorder<Key>(e, in, out, pin, pout, count, shift, RSX_RADIX - 1, next_shift, cx);
         }
         if (rc != RSX_OK) return rc;
         in = out;
@@ -1243,11 +1384,13 @@ int rsx_device_name(int device, char* buf, size_t buflen)
     return RSX_OK;
 }
 
-int rsx_create(rsx_engine** out, int device, int key_bytes, int is_signed, int has_payload, uint64_t capacity)
+int rsx_create(rsx_engine** out, int device, int key_bytes, int key_kind, int has_payload, uint64_t capacity)
 {
     if (!out) return fail(RSX_INITIALIZATION_FAILED, "rsx_create: null out pointer");
     *out = nullptr;
     if (key_bytes != 4 && key_bytes != 8) return fail(RSX_INITIALIZATION_FAILED, "rsx_create: key_bytes must be 4 or 8");
+    if (key_kind < RSX_KEY_UNSIGNED || key_kind > RSX_KEY_FLOAT)
+        return fail(RSX_INITIALIZATION_FAILED, "rsx_create: key_kind must be RSX_KEY_UNSIGNED (0), RSX_KEY_SIGNED (1) or RSX_KEY_FLOAT (2)");
     if (capacity == 0 || capacity > 0xFFFFFFFFull) {
         return fail(RSX_RESIZE_FAILED, "rsx_create: capacity must be in [1, 2^32-1] (32-bit slots)");
     }
@@ -1261,7 +1404,8 @@ int rsx_create(rsx_engine** out, int device, int key_bytes, int is_signed, int h
     if (!e) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_create: out of host memory");
     e->device = device;
     e->key_bytes = key_bytes;
-    e->is_signed = is_signed != 0;
+    e->key_kind = key_kind;
+    e->is_signed = key_kind == RSX_KEY_SIGNED;
     e->has_payload = has_payload != 0;
     e->capacity = capacity;
     e->n = 0;
@@ -1377,13 +1521,19 @@ int rsx_create(rsx_engine** out, int device, int key_bytes, int is_signed, int h
         if (allow_tile(reinterpret_cast<const void*>(&rsx::tile_sort_kernel<uint32_t, kTileThreads, kKeysPerThread, false>), L32::BYTES) != hipSuccess ||
             allow_tile(reinterpret_cast<const void*>(&rsx::tile_sort_kernel<uint32_t, kTileThreads, kKeysPerThread, true>), L32::BYTES) != hipSuccess ||
             allow_tile(reinterpret_cast<const void*>(&rsx::tile_sort_kernel<uint64_t, kTileThreads, kKeysPerThread, false>), L64::BYTES) != hipSuccess ||
-            allow_tile(reinterpret_cast<const void*>(&rsx::tile_sort_kernel<uint64_t, kTileThreads, kKeysPerThread, true>), L64::BYTES) != hipSuccess)
+            allow_tile(reinterpret_cast<const void*>(&rsx::tile_sort_kernel<uint64_t, kTileThreads, kKeysPerThread, true>), L64::BYTES) != hipSuccess ||
+            allow_tile(reinterpret_cast<const void*>(&rsx::tile_sort_kernel<uint32_t, kTileThreads, kKeysPerThread, false, true>), L32::BYTES) != hipSuccess ||
+            allow_tile(reinterpret_cast<const void*>(&rsx::tile_sort_kernel<uint32_t, kTileThreads, kKeysPerThread, true, true>), L32::BYTES) != hipSuccess ||
+            allow_tile(reinterpret_cast<const void*>(&rsx::tile_sort_kernel<uint64_t, kTileThreads, kKeysPerThread, false, true>), L64::BYTES) != hipSuccess ||
+            allow_tile(reinterpret_cast<const void*>(&rsx::tile_sort_kernel<uint64_t, kTileThreads, kKeysPerThread, true, true>), L64::BYTES) != hipSuccess)
             rc = fail(RSX_INITIALIZATION_FAILED, "hipFuncSetAttribute(tile_sort_kernel)");
     }
 #endif
 #if RSX_PRODUCT_SHAPE
     if (rc == RSX_OK) rc = allow_lds<uint64_t, true, false, false, 8, 512>();
     if (rc == RSX_OK) rc = allow_lds<uint64_t, true, true, false, 8, 512>();
+    if (rc == RSX_OK) rc = allow_lds<uint64_t, true, false, false, 8, 512, true>();
+    if (rc == RSX_OK) rc = allow_lds<uint64_t, true, true, false, 8, 512, true>();
 #endif
     if (rc == RSX_OK) rc = allow_lds<uint32_t, false, false>();
     if (rc == RSX_OK) rc = allow_lds<uint32_t, true, false>();
@@ -1397,6 +1547,15 @@ int rsx_create(rsx_engine** out, int device, int key_bytes, int is_signed, int h
     if (rc == RSX_OK) rc = allow_lds<uint32_t, true, false, true>();
     if (rc == RSX_OK) rc = allow_lds<uint64_t, false, false, true>();
     if (rc == RSX_OK) rc = allow_lds<uint64_t, true, false, true>();
+    // the first and last pass of a float / descending sort
+    if (rc == RSX_OK) rc = allow_lds<uint32_t, false, false, false, kKeysPerThread, kTileThreads, true>();
+    if (rc == RSX_OK) rc = allow_lds<uint32_t, true, false, false, kKeysPerThread, kTileThreads, true>();
+    if (rc == RSX_OK) rc = allow_lds<uint64_t, false, false, false, kKeysPerThread, kTileThreads, true>();
+    if (rc == RSX_OK) rc = allow_lds<uint64_t, true, false, false, kKeysPerThread, kTileThreads, true>();
+    if (rc == RSX_OK) rc = allow_lds<uint32_t, false, true, false, kKeysPerThread, kTileThreads, true>();
+    if (rc == RSX_OK) rc = allow_lds<uint32_t, true, true, false, kKeysPerThread, kTileThreads, true>();
+    if (rc == RSX_OK) rc = allow_lds<uint64_t, false, true, false, kKeysPerThread, kTileThreads, true>();
+    if (rc == RSX_OK) rc = allow_lds<uint64_t, true, true, false, kKeysPerThread, kTileThreads, true>();
     if (rc != RSX_OK) {
         rsx_destroy(e);
         return rc;
@@ -1506,7 +1665,15 @@ int rsx_set_option(rsx_engine* e, int option, int64_t value)
     case RSX_OPT_PROFILE: e->profile = value < 0 || value > 2 ? 1 : static_cast<int>(value); return RSX_OK;
     case RSX_OPT_XCD_REMAP: e->xcd_remap = value != 0; return RSX_OK;
     case RSX_OPT_LOOKAHEAD: e->lookahead = value != 0; return RSX_OK;
-    case RSX_OPT_REF_DIAGNOSTICS: e->ref_diag = value != 0; return RSX_OK;
+    case RSX_OPT_REF_DIAGNOSTICS:
+        if (value != 0 && e->codec()) return refuse_codec("RSX_OPT_REF_DIAGNOSTICS");
+        e->ref_diag = value != 0;
+        return RSX_OK;
+    case RSX_OPT_DESCENDING:
+        if (value != 0 && e->ref_diag) return refuse_codec("RSX_OPT_DESCENDING with RSX_OPT_REF_DIAGNOSTICS");
+        e->descending = value != 0;
+        e->radix8_ready = false;         // the codec's 8-bit scatter kernels get their LDS allowance on the next ensure_radix8
+        return RSX_OK;
     case RSX_OPT_GRAPH: e->use_graph = value != 0; return RSX_OK;
     case RSX_OPT_SMALL_SCAN: e->small_scan = value != 0; return RSX_OK;
     case RSX_OPT_TILE_SORT: e->tile_sort = value != 0; return RSX_OK;
@@ -1638,13 +1805,18 @@ int rsx_fill_pad(rsx_engine* e, uint64_t byte_offset)
     if (count == 0) return RSX_OK;
     if (bind_device(e, RSX_CALCULATION_FAILED) != RSX_OK) return RSX_CALCULATION_FAILED;
     const uint32_t blocks = static_cast<uint32_t>(std::min<uint64_t>((count + 255) / 256, 2048));
+    // the key whose encoding is all-ones - 1 (the key that sorts next-to-last): numeric_limits<T>::max() - 1 for integer keys in
+    // ascending order (RadixSortGPU.cpp:274-276)
     if (e->key_bytes == 4) {
-        // numeric_limits<T>::max() - 1 (RadixSortGPU.cpp:274-276)
-        const uint32_t v = e->is_signed ? 0x7FFFFFFEu : 0xFFFFFFFEu;
+        uint32_t a = 0, m = 0;
+        order_consts<uint32_t>(e, &a, &m);
+        const uint32_t v = codec_decode_host<uint32_t>(0xFFFFFFFEu, a, m);
         hipLaunchKernelGGL(rsx::fill_kernel<uint32_t>, dim3(blocks), dim3(256), 0, e->stream, static_cast<uint32_t*>(e->keys[e->cur]),
                            first, count, v);
     } else {
-        const uint64_t v = e->is_signed ? 0x7FFFFFFFFFFFFFFEull : 0xFFFFFFFFFFFFFFFEull;
+        uint64_t a = 0, m = 0;
+        order_consts<uint64_t>(e, &a, &m);
+        const uint64_t v = codec_decode_host<uint64_t>(0xFFFFFFFFFFFFFFFEull, a, m);
         hipLaunchKernelGGL(rsx::fill_kernel<uint64_t>, dim3(blocks), dim3(256), 0, e->stream, static_cast<uint64_t*>(e->keys[e->cur]),
                            first, count, v);
     }
@@ -1812,8 +1984,10 @@ int rsx_histogram(rsx_engine* e, int pass)
     if (!e) return fail(RSX_CALCULATION_FAILED, "rsx_histogram: null engine");
     if (pass < 0 || pass >= static_cast<int>(e->passes())) return fail(RSX_CALCULATION_FAILED, "rsx_histogram: pass out of range");
     if (bind_device(e, RSX_CALCULATION_FAILED) != RSX_OK) return RSX_CALCULATION_FAILED;
-    return RSX_BY_KEY(e, launch_histogram<uint32_t>(e, e->keys[e->cur], e->n, pass * RSX_RADIX_BITS, RSX_RADIX - 1),
-                      launch_histogram<uint64_t>(e, e->keys[e->cur], e->n, pass * RSX_RADIX_BITS, RSX_RADIX - 1));
+    // (a codec engine's step API encodes at pass == RSX_OPT_FIRST_PASS and decodes at pass + 1 == RSX_OPT_LAST_PASS)
+    const int cx = pass_codec(e, pass, 1, e->first_pass, e->last_pass) & kEncode;
+    return RSX_BY_KEY(e, launch_histogram<uint32_t>(e, e->keys[e->cur], e->n, pass * RSX_RADIX_BITS, RSX_RADIX - 1, 0u, 0u, 0, cx),
+                      launch_histogram<uint64_t>(e, e->keys[e->cur], e->n, pass * RSX_RADIX_BITS, RSX_RADIX - 1, 0ull, 0ull, 0, cx));
 }
 
 int rsx_scan(rsx_engine* e)
@@ -1838,8 +2012,9 @@ int rsx_reorder(rsx_engine* e, int pass)
     const int src = e->cur, dst = e->cur ^ 1;
     const uint32_t* pin = e->has_payload ? e->perm[src] : nullptr;
     uint32_t* pout = e->has_payload ? e->perm[dst] : nullptr;
-    const int rc = RSX_BY_KEY(e, launch_reorder<uint32_t>(e, e->keys[src], e->keys[dst], pin, pout, e->n, pass * RSX_RADIX_BITS, RSX_RADIX - 1),
-                              launch_reorder<uint64_t>(e, e->keys[src], e->keys[dst], pin, pout, e->n, pass * RSX_RADIX_BITS, RSX_RADIX - 1));
+    const int cx = pass_codec(e, pass, 1, e->first_pass, e->last_pass);
+    const int rc = RSX_BY_KEY(e, launch_reorder<uint32_t>(e, e->keys[src], e->keys[dst], pin, pout, e->n, pass * RSX_RADIX_BITS, RSX_RADIX - 1, -1, cx),
+                              launch_reorder<uint64_t>(e, e->keys[src], e->keys[dst], pin, pout, e->n, pass * RSX_RADIX_BITS, RSX_RADIX - 1, -1, cx));
     if (rc != RSX_OK) return rc;
     e->cur = dst;   // swap of the buffer names (RadixSortGPU.cpp:263-266)
     e->result_external = false;
@@ -1934,6 +2109,7 @@ int rsx_partition(rsx_engine* e, const void* d_keys, const uint32_t* d_payload, 
                   uint32_t* d_payload_out, uint64_t* bucket_offsets)
 {
     if (!e || !bucket_offsets) return fail(RSX_CALCULATION_FAILED, "rsx_partition: null argument");
+    if (e->codec()) return refuse_codec("rsx_partition");
     if (bits < 0 || bits > RSX_RADIX_BITS || shift < 0 || shift + bits > e->key_bytes * 8)
         return fail(RSX_CALCULATION_FAILED, "rsx_partition: bit field out of range (at most 4 bits)");
     if (n > e->capacity) return fail(RSX_RESIZE_FAILED, "rsx_partition: beyond capacity");
@@ -1966,6 +2142,7 @@ int rsx_partition(rsx_engine* e, const void* d_keys, const uint32_t* d_payload, 
 int rsx_partition_count(rsx_engine* e, const void* d_keys, uint64_t n, int shift, int bits, uint64_t* bucket_counts)
 {
     if (!e || !bucket_counts) return fail(RSX_CALCULATION_FAILED, "rsx_partition_count: null argument");
+    if (e->codec()) return refuse_codec("rsx_partition_count");
     if (bits < 0 || bits > RSX_RADIX_BITS || shift < 0 || shift + bits > e->key_bytes * 8)
         return fail(RSX_CALCULATION_FAILED, "rsx_partition_count: bit field out of range (at most 4 bits)");
     if (n > e->capacity) return fail(RSX_RESIZE_FAILED, "rsx_partition_count: beyond capacity");
@@ -1992,6 +2169,7 @@ int rsx_partition_scatter(rsx_engine* e, const void* d_keys, const uint32_t* d_p
                           void* d_keys_out, uint32_t* d_payload_out)
 {
     if (!e) return fail(RSX_CALCULATION_FAILED, "rsx_partition_scatter: null engine");
+    if (e->codec()) return refuse_codec("rsx_partition_scatter");
     if (n == 0) {
         e->counted_keys = nullptr;
         return RSX_OK;
@@ -2018,6 +2196,7 @@ int rsx_partition_scatter(rsx_engine* e, const void* d_keys, const uint32_t* d_p
 int rsx_sample_keys(rsx_engine* e, const void* d_keys, uint64_t n, uint32_t count, uint64_t* samples)
 {
     if (!e || !samples) return fail(RSX_CALCULATION_FAILED, "rsx_sample_keys: null argument");
+    if (e->codec()) return refuse_codec("rsx_sample_keys");
     if (count == 0 || count > static_cast<uint32_t>(kRangeBlocks) * 2) return fail(RSX_CALCULATION_FAILED, "rsx_sample_keys: count must be in [1, 4096]");
     if (n == 0 || !d_keys) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_sample_keys: no keys");
     if (bind_device(e, RSX_CALCULATION_FAILED) != RSX_OK) return RSX_CALCULATION_FAILED;
@@ -2038,6 +2217,7 @@ int rsx_sample_keys(rsx_engine* e, const void* d_keys, uint64_t n, uint32_t coun
 int rsx_partition_count_split(rsx_engine* e, const void* d_keys, uint64_t n, const uint64_t* splitters, int nsplit, uint64_t* bucket_counts)
 {
     if (!e || !bucket_counts || (nsplit > 0 && !splitters)) return fail(RSX_CALCULATION_FAILED, "rsx_partition_count_split: null argument");
+    if (e->codec()) return refuse_codec("rsx_partition_count_split");
     if (nsplit < 1 || nsplit > 7) return fail(RSX_CALCULATION_FAILED, "rsx_partition_count_split: 1..7 splitters");
     for (int k = 1; k < nsplit; ++k) {
         if (splitters[k] <= splitters[k - 1]) return fail(RSX_CALCULATION_FAILED, "rsx_partition_count_split: splitters must be strictly increasing");
@@ -2071,6 +2251,7 @@ int rsx_partition_count_split(rsx_engine* e, const void* d_keys, uint64_t n, con
 int rsx_partition_scatter_split(rsx_engine* e, const void* d_keys, const uint32_t* d_payload, uint64_t n, void* d_keys_out, uint32_t* d_payload_out)
 {
     if (!e) return fail(RSX_CALCULATION_FAILED, "rsx_partition_scatter_split: null engine");
+    if (e->codec()) return refuse_codec("rsx_partition_scatter_split");
     if (n == 0) {
         e->counted_keys = nullptr;
         return RSX_OK;
@@ -2167,6 +2348,7 @@ int rsx_peer_enable(rsx_engine* e, int peer_device)
 int rsx_key_range(rsx_engine* e, const void* d_keys, uint64_t n, uint64_t* lo, uint64_t* hi)
 {
     if (!e || !lo || !hi) return fail(RSX_CALCULATION_FAILED, "rsx_key_range: null argument");
+    if (e->codec()) return refuse_codec("rsx_key_range");
     *lo = ~0ull;
     *hi = 0ull;
     if (n == 0) return RSX_OK;
@@ -2179,6 +2361,7 @@ int rsx_partition_range(rsx_engine* e, const void* d_keys, const uint32_t* d_pay
                         void* d_keys_out, uint32_t* d_payload_out, uint64_t* bucket_offsets)
 {
     if (!e || !bucket_offsets) return fail(RSX_CALCULATION_FAILED, "rsx_partition_range: null argument");
+    if (e->codec()) return refuse_codec("rsx_partition_range");
     if (shift < 0 || shift >= e->key_bytes * 8) return fail(RSX_CALCULATION_FAILED, "rsx_partition_range: shift out of range");
     if (n > e->capacity) return fail(RSX_RESIZE_FAILED, "rsx_partition_range: beyond capacity");
     if (n > 0 && (!d_keys || !d_keys_out || !aligned16(d_keys) || !aligned16(d_keys_out)))

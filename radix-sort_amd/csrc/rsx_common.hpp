@@ -47,6 +47,34 @@ __device__ __forceinline__ uint32_t digit_of(Key key, int shift, Key flip, uint3
     return static_cast<uint32_t>((key ^ flip) >> shift) & mask;
 }
 
+// Key codec of float and descending engines: an order-preserving bijection on the key bits, so that the passes sort plain
+// unsigned keys.  With B the key width and two uniform constants (A, M) per direction:
+//   encode  z = x ^ ((x >>arith (B-1)) & M);  y = z ^ A
+//   decode  z = y ^ A;  x = z ^ ((z >>arith (B-1)) & M)
+// float ascending (A, M) = (signbit, ~signbit) [IEEE 754 totalOrder]; float descending (~signbit, ~signbit); integer descending
+// (~flip, 0); (0, 0) is the identity.  The first pass of a sort encodes as it loads, the last one decodes as it stores (the
+// other direction's constants are zero in those launches); memory between passes holds encoded keys.
+template <typename Key>
+struct KeyCodec {
+    Key ea, em;     // encode on load
+    Key da, dm;     // decode on store
+};
+
+__device__ __forceinline__ uint32_t sign_fill(uint32_t x) { return static_cast<uint32_t>(static_cast<int32_t>(x) >> 31); }
+__device__ __forceinline__ uint64_t sign_fill(uint64_t x) { return static_cast<uint64_t>(static_cast<int64_t>(x) >> 63); }
+
+template <typename Key>
+__device__ __forceinline__ Key codec_encode(Key x, Key a, Key m)
+{
+    return (x ^ (sign_fill(x) & m)) ^ a;
+}
+template <typename Key>
+__device__ __forceinline__ Key codec_decode(Key y, Key a, Key m)
+{
+    const Key z = y ^ a;
+    return z ^ (sign_fill(z) & m);
+}
+
 // Bucket of the multi-GPU partition pass: x = (key ^ sign) - lo, 16 equal-width buckets over the
 // global key range.  mul != 0: floor(x * 16 / (hi - lo + 1)) as a multiply-high by
 // mul = floor(16 * 2^W / (hi - lo + 1)); mul == 0 (ranges of at most 16 values): x >> shift.

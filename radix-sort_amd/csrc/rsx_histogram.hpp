@@ -15,19 +15,24 @@ namespace rsx {
 // banks instead of serialising on one address.
 // RANGED (multi-GPU partition only): bucket = ranged_bucket((key ^ flip) - lo) — 16 equal-width
 // buckets over the global key range [lo, hi], a monotone function of the key.
-template <typename Key, int THREADS, int KPT, bool RANGED = false>
+// CODEC: the first pass of a float / descending sort counts the digits of the ENCODED keys (rsx_common.hpp, KeyCodec).
+template <typename Key, int THREADS, int KPT, bool RANGED = false, bool CODEC = false>
 __global__ __launch_bounds__(THREADS) void histogram_kernel(const Key* __restrict__ keys, uint32_t* __restrict__ table,
                                                              uint64_t n, uint32_t ntiles, uint32_t tiles_per_xcd,
                                                              int remap, int shift, Key flip, uint32_t mask, Key lo, Key mul,
                                                              SplitSet<Key> split, uint32_t* __restrict__ rows_out = nullptr,
-                                                             uint32_t* __restrict__ zero_a = nullptr, uint32_t* __restrict__ zero_b = nullptr)
+                                                             uint32_t* __restrict__ zero_a = nullptr, uint32_t* __restrict__ zero_b = nullptr,
+                                                             KeyCodec<Key> codec = KeyCodec<Key>{})
 {
+    static_assert(!(RANGED && CODEC), "the partition passes have no codec");
     auto dig = [=](Key key) -> uint32_t {
         if constexpr (RANGED) {
             if (split.n) {
                 return splitter_bucket(static_cast<Key>(key ^ flip), split);
             }
             return ranged_bucket(static_cast<Key>((key ^ flip) - lo), shift, mul, mask);
+        } else if constexpr (CODEC) {
+            return digit_of(codec_encode(key, codec.ea, codec.em), shift, flip, mask);
         } else {
             return digit_of(key, shift, flip, mask);
         }

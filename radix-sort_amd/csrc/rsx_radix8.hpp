@@ -32,10 +32,42 @@ __device__ __forceinline__ uint32_t digit8_of(Key key, int shift, Key flip)
     return static_cast<uint32_t>((key ^ flip) >> shift) & 255u;
 }
 
-template <typename Key, int THREADS, int KPT>
-__global__ __launch_bounds__(THREADS) void histogram8_kernel(const Key* __restrict__ keys, uint32_t* __restrict__ counts8, uint64_t n, uint32_t ntiles,
-                                                              uint32_t tiles_per_xcd, int remap, int shift, Key flip)
+// Codec of the 8-bit passes (float / descending engines, rsx_common.hpp KeyCodec): the first pass of the chain encodes, the last one
+// decodes, the passes between see encoded keys in memory.  PACKED32 elements carry the key in their low word: only that half is coded.
+template <typename Key, bool PACKED32>
+using Codec8 = KeyCodec<typename std::conditional<PACKED32, uint32_t, Key>::type>;
+
+template <bool PACKED32, typename Key, typename CK>
+__device__ __forceinline__ Key elem_encode(Key x, const KeyCodec<CK>& c)
 {
+    if constexpr (PACKED32) {
+        return (x & ~Key{0xFFFFFFFFu}) | static_cast<Key>(codec_encode(static_cast<uint32_t>(x), c.ea, c.em));
+    } else {
+        return codec_encode(x, c.ea, c.em);
+    }
+}
+template <bool PACKED32, typename Key, typename CK>
+__device__ __forceinline__ Key elem_decode(Key x, const KeyCodec<CK>& c)
+{
+    if constexpr (PACKED32) {
+        return (x & ~Key{0xFFFFFFFFu}) | static_cast<Key>(codec_decode(static_cast<uint32_t>(x), c.da, c.dm));
+    } else {
+        return codec_decode(x, c.da, c.dm);
+    }
+}
+
+template <typename Key, int THREADS, int KPT, bool CODEC = false>
+__global__ __launch_bounds__(THREADS) void histogram8_kernel(const Key* __restrict__ keys, uint32_t* __restrict__ counts8, uint64_t n, uint32_t ntiles,
+                                                              uint32_t tiles_per_xcd, int remap, int shift, Key flip,
+                                                              KeyCodec<Key> codec = KeyCodec<Key>{})
+{
+    auto d8 = [=](Key key) -> uint32_t {
+        if constexpr (CODEC) {
+            return digit8_of(codec_encode(key, codec.ea, codec.em), shift, flip);
+        } else {
+            return digit8_of(key, shift, flip);
+        }
+    };
     static_assert(THREADS == kRadix8, "one thread per digit writes the tile's row");
     constexpr int TILE = THREADS * KPT;
     constexpr int VEC = KeyVec<Key>::N;
@@ -60,13 +92,13 @@ __global__ __launch_bounds__(THREADS) void histogram8_kernel(const Key* __restri
         }
         // a wave whose keys all share the digit (constant or sorted data) would serialise 64 lanes on one LDS
         // address per key: the first key stands for the wave, as in reorder_kernel's look-ahead
-        const uint32_t d0 = digit8_of(v[0].k[0], shift, flip);
+        const uint32_t d0 = d8(v[0].k[0]);
         const bool spread = __ballot(d0 != static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(d0)))) != 0ull;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
-                const uint32_t d = digit8_of(v[j].k[e], shift, flip);
+                const uint32_t d = d8(v[j].k[e]);
                 if (spread) {
                     atomicAdd(&cnt[d], 1u);
                 } else {
@@ -88,7 +120,7 @@ __global__ __launch_bounds__(THREADS) void histogram8_kernel(const Key* __restri
             for (int e = 0; e < VEC; ++e) {
                 const uint32_t li = static_cast<uint32_t>(j) * THREADS * VEC + tid * VEC + e;
                 if (li < valid) {
-                    atomicAdd(&cnt[digit8_of(keys[base + li], shift, flip)], 1u);
+                    atomicAdd(&cnt[d8(keys[base + li])], 1u);
                 }
             }
         }
@@ -239,10 +271,12 @@ __device__ __forceinline__ void reorder8_partial_tile_loaded()
 
 // FULL_ONLY: the tile is known to be whole — vector loads and no branch (what a prefetch across a loop iteration needs: the wait counters of
 // loads issued under a branch are merged conservatively at the join, and the first use behind it would wait for everything).
-template <typename Key, int THREADS, int KPT, bool PAYLOAD, bool PACKED32, bool FULL_ONLY = false>
+// CODEC: the pads are the elements whose key encodes to all-ones.
+template <typename Key, int THREADS, int KPT, bool PAYLOAD, bool PACKED32, bool FULL_ONLY = false, bool CODEC = false>
 __device__ __forceinline__ void reorder8_fetch(Reorder8Regs<Key, KPT, PAYLOAD>& t, const Key* __restrict__ in, const uint32_t* __restrict__ pin,
                                                const uint32_t* __restrict__ table8, const uint32_t* __restrict__ gsum8, const uint32_t* __restrict__ cbase8,
-                                               uint32_t chunk_groups, uint64_t n, uint32_t tile, Key flip)
+                                               uint32_t chunk_groups, uint64_t n, uint32_t tile, Key flip,
+                                               const Codec8<Key, PACKED32>& codec = Codec8<Key, PACKED32>{})
 {
     constexpr int TILE = THREADS * KPT;
     constexpr int VEC = KeyVec<Key>::N;
@@ -254,7 +288,13 @@ __device__ __forceinline__ void reorder8_fetch(Reorder8Regs<Key, KPT, PAYLOAD>& 
     const bool full = FULL_ONLY || (valid == TILE);
     t.valid = valid;
     // pads sort behind every real key of the tile (digit 255 once the flip below is applied)
-    const Key pad_raw = static_cast<Key>(~Key{0}) ^ flip;
+    Key pad_raw = static_cast<Key>(~Key{0}) ^ flip;
+    if constexpr (CODEC) {
+        Codec8<Key, PACKED32> inverse = codec;          // decode with the ENCODE constants: the preimage of all-ones
+        inverse.da = codec.ea;
+        inverse.dm = codec.em;
+        pad_raw = elem_decode<PACKED32>(static_cast<Key>(~Key{0}), inverse);
+    }
     // this thread's digit of the tile's table row (latency hides under the key loads): global slot of the tile's first key with
     // that digit minus its tile-local slot
     const uint32_t group = tile / kScan8Tiles;
@@ -318,8 +358,9 @@ __device__ __forceinline__ void reorder8_fetch(Reorder8Regs<Key, KPT, PAYLOAD>& 
 // payloads — as runs at their global slots.  Ends with a barrier: the image, the counters and gb[] are free for the next tile.
 // UNROLL_ROUNDS: both rounds written out.  The staying kernel needs it: on gfx9 (stores count in vmcnt) the compiler drains vmcnt to 0 in the
 // preheader of a loop that stores and uses registers loaded before it — which would end the prefetch of the next tile right there.
-template <typename Key, int THREADS, int KPT, bool PAYLOAD, bool PACKED32, bool UNROLL_ROUNDS = false>
-__device__ __forceinline__ void reorder8_sort_tile(Reorder8Regs<Key, KPT, PAYLOAD>& t, uint32_t* smem, Key* __restrict__ out, uint32_t* __restrict__ pout, int shift, Key flip)
+template <typename Key, int THREADS, int KPT, bool PAYLOAD, bool PACKED32, bool UNROLL_ROUNDS = false, bool CODEC = false>
+__device__ __forceinline__ void reorder8_sort_tile(Reorder8Regs<Key, KPT, PAYLOAD>& t, uint32_t* smem, Key* __restrict__ out, uint32_t* __restrict__ pout, int shift, Key flip,
+                                                   const Codec8<Key, PACKED32>& codec = Codec8<Key, PACKED32>{})
 {
     using L = Reorder8Layout<Key, THREADS, KPT, PAYLOAD>;
     constexpr int TILE = THREADS * KPT;
@@ -342,6 +383,12 @@ __device__ __forceinline__ void reorder8_sort_tile(Reorder8Regs<Key, KPT, PAYLOA
 #pragma unroll
         for (int i = 0; i < KPT; ++i) {
             t.k[i] ^= flip;
+        }
+    }
+    if constexpr (CODEC) {          // (codec engines run with flip = 0)
+#pragma unroll
+        for (int i = 0; i < KPT; ++i) {
+            t.k[i] = elem_encode<PACKED32>(t.k[i], codec);
         }
     }
     if (THREADS == kRadix8 || tid < static_cast<uint32_t>(kRadix8)) {
@@ -457,6 +504,12 @@ __device__ __forceinline__ void reorder8_sort_tile(Reorder8Regs<Key, KPT, PAYLOA
                     okey[r] ^= flip;
                 }
             }
+            if constexpr (CODEC) {
+#pragma unroll
+                for (int r = 0; r < KPT; ++r) {
+                    okey[r] = elem_decode<PACKED32>(okey[r], codec);
+                }
+            }
             if constexpr (PACKED32) {
                 uint32_t* out32 = reinterpret_cast<uint32_t*>(out);
                 // (key and payload of a slot together: all keys first, then all payloads, is 7 % slower — r03_ab_split_stores.txt)
@@ -522,11 +575,12 @@ __device__ __forceinline__ void reorder8_sort_tile(Reorder8Regs<Key, KPT, PAYLOA
 // rounds as ONE 64-bit element (key in the low word, where the digit is taken; payload in the high word) — `in` / `out` really point at
 // uint32 keys, `pin` / `pout` at the payloads.  One 8-byte LDS access per element and round instead of two 4-byte ones, and none of the
 // payload's own trips (4 barriers fewer per tile): the uint32 + payload scatter then costs what the uint64 keys-only one costs.
-template <typename Key, int THREADS, int KPT, bool PAYLOAD, bool PACKED32 = false>
+template <typename Key, int THREADS, int KPT, bool PAYLOAD, bool PACKED32 = false, bool CODEC = false>
 __global__ __launch_bounds__(THREADS, (PAYLOAD ? (THREADS > 256 ? 4 : 2) : (Reorder8Layout<Key, THREADS, KPT>::MIN_WAVES > 4 ? 4 : Reorder8Layout<Key, THREADS, KPT>::MIN_WAVES))) void reorder8_kernel(
     const Key* __restrict__ in, Key* __restrict__ out, const uint32_t* __restrict__ pin, uint32_t* __restrict__ pout,
     const uint32_t* __restrict__ table8, const uint32_t* __restrict__ gsum8, const uint32_t* __restrict__ cbase8,
-    uint32_t chunk_groups, uint64_t n, uint32_t ntiles, uint32_t tiles_per_xcd, int remap, int shift, Key flip)
+    uint32_t chunk_groups, uint64_t n, uint32_t ntiles, uint32_t tiles_per_xcd, int remap, int shift, Key flip,
+    Codec8<Key, PACKED32> codec = Codec8<Key, PACKED32>{})
 {
     static_assert(!PACKED32 || (sizeof(Key) == 8 && !PAYLOAD), "packed (uint32 key, payload) elements are 64-bit and carry their payload themselves");
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -536,8 +590,8 @@ __global__ __launch_bounds__(THREADS, (PAYLOAD ? (THREADS > 256 ? 4 : 2) : (Reor
     }
     // (lds_store_at addresses the image from LDS address 0: checked once on the host, rsx_create)
     Reorder8Regs<Key, KPT, PAYLOAD> t;
-    reorder8_fetch<Key, THREADS, KPT, PAYLOAD, PACKED32>(t, in, pin, table8, gsum8, cbase8, chunk_groups, n, tile, flip);
-    reorder8_sort_tile<Key, THREADS, KPT, PAYLOAD, PACKED32>(t, smem, out, pout, shift, flip);
+    reorder8_fetch<Key, THREADS, KPT, PAYLOAD, PACKED32, false, CODEC>(t, in, pin, table8, gsum8, cbase8, chunk_groups, n, tile, flip, codec);
+    reorder8_sort_tile<Key, THREADS, KPT, PAYLOAD, PACKED32, false, CODEC>(t, smem, out, pout, shift, flip, codec);
 }
 
 }  // namespace rsx

@@ -189,15 +189,20 @@ struct InlineScanArgs {
 // counters, the run bases and the flushed counts are PLACED (flip_cur / flip_next below).
 // INLINE_SCAN kernels are instantiated by the experiments build only (-DRSX_EXPERIMENTS: measured slower than the scan launch they remove); the fused-scan
 // body they carry needs registers of its own (142 VGPRs): three waves per SIMD are asked of them, otherwise the uint32 variants spill (52-180 bytes per lane in round 3).
-template <typename Key, int THREADS, int KPT, bool PAYLOAD, bool LOOKAHEAD, bool RANGED = false, bool INLINE_SCAN = false>
+// CODEC (first and last pass of a float / descending sort, rsx_common.hpp KeyCodec): keys are encoded right after the load — the
+// RAW digits, the staging image and the look-ahead counts all see encoded keys — and decoded on their way out; pads are the encoded
+// all-ones key.  Such engines run with flip = 0 throughout, and their middle passes take the plain kernels.
+template <typename Key, int THREADS, int KPT, bool PAYLOAD, bool LOOKAHEAD, bool RANGED = false, bool INLINE_SCAN = false, bool CODEC = false>
 __global__ __launch_bounds__(THREADS, (INLINE_SCAN ? 3 : reorder_min_waves<Key, THREADS, KPT, PAYLOAD, RANGED>())) void reorder_kernel(const Key* __restrict__ in, Key* __restrict__ out,
                                                            const uint32_t* __restrict__ pin, uint32_t* __restrict__ pout,
                                                            const uint32_t* table, uint64_t n, uint32_t ntiles,
                                                            uint32_t tiles_per_xcd, int remap, int shift, Key flip, uint32_t mask,
                                                            uint32_t* __restrict__ next_counts, int next_shift,
                                                            const uint32_t* __restrict__ globsum, Key lo, Key mul,
-                                                           SplitSet<Key> split, SelfScanArgs self, InlineScanArgs iscan = InlineScanArgs{})
+                                                           SplitSet<Key> split, SelfScanArgs self, InlineScanArgs iscan = InlineScanArgs{},
+                                                           KeyCodec<Key> codec = KeyCodec<Key>{})
 {
+    static_assert(!CODEC || (!RANGED && !INLINE_SCAN), "the codec serves rsx_sort's passes and the step API only");
     static_assert(!INLINE_SCAN || (!RANGED && THREADS == kScanTiles), "the inline scan is the fused scan's workgroup: 256 threads, rsx_sort's passes only");
     using L = ReorderLayout<Key, THREADS, KPT>;
     static_assert(!(RANGED && LOOKAHEAD), "the ranged bucket function is for the one-pass partition only");
@@ -237,7 +242,8 @@ __global__ __launch_bounds__(THREADS, (INLINE_SCAN ? 3 : reorder_min_waves<Key, 
     const bool full = (valid == TILE);
     // Slots past `valid` hold a key whose digit is 15 in every pass; being last in index
     // order as well they land in local slots [valid, TILE) and are never stored.
-    const Key pad_key = static_cast<Key>(~flip);
+    // (CODEC: the key that encodes to all-ones, so that the encode below turns it into the pad)
+    const Key pad_key = CODEC ? codec_decode(static_cast<Key>(~Key{0}), codec.ea, codec.em) : static_cast<Key>(~flip);
 #ifdef RSX_STAMPS
     unsigned long long* stamp_buf = reinterpret_cast<unsigned long long*>(const_cast<uint32_t*>(globsum));
     globsum = nullptr;
@@ -314,6 +320,12 @@ __global__ __launch_bounds__(THREADS, (INLINE_SCAN ? 3 : reorder_min_waves<Key, 
         for (int i = 0; i < KPT; ++i) {
             const uint32_t li = tid * KPT + i;
             k[i] = li < valid ? in[base + li] : pad_key;
+        }
+    }
+    if constexpr (CODEC) {
+#pragma unroll
+        for (int i = 0; i < KPT; ++i) {
+            k[i] = codec_encode(k[i], codec.ea, codec.em);
         }
     }
     // payload of the thread's blocked keys straight from HBM (64 B contiguous per lane)
@@ -618,6 +630,12 @@ __global__ __launch_bounds__(THREADS, (INLINE_SCAN ? 3 : reorder_min_waves<Key, 
     RSX_STAMP(6);
     // keys leave first, then the look-ahead counts: both free their registers before the
     // payload takes its own trip through the staging image
+    if constexpr (CODEC) {
+#pragma unroll
+        for (int r = 0; r < KPT; ++r) {
+            okey[r] = codec_decode(okey[r], codec.da, codec.dm);      // (the look-ahead indices above were taken from the encoded keys)
+        }
+    }
     if (full) {
 #pragma unroll
         for (int r = 0; r < KPT; ++r) {

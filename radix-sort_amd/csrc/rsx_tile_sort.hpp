@@ -31,12 +31,14 @@ struct TileSortLayout {
     static_assert(ROW_DW % 4 == 0 && KPT == 16, "row geometry (slot >> 4 selects the row)");
 };
 
-template <typename Key, int THREADS, int KPT, bool PAYLOAD>
+// CODEC (float / descending engines): keys are encoded as they are loaded and decoded as they are stored; in between, pads
+// included (the encoded all-ones key), everything lives in the encoded domain.
+template <typename Key, int THREADS, int KPT, bool PAYLOAD, bool CODEC = false>
 __global__ __launch_bounds__(THREADS) void tile_sort_kernel(const Key* in, Key* out, Key* before_last,        // may alias each other: everything
                                                             const uint32_t* pin, uint32_t* pout, uint32_t* pbefore_last,            // is read before anything is written
                                                             uint32_t n, int first_pass, int last_pass,
                                                             Key flip, uint32_t* __restrict__ table, uint32_t* __restrict__ globsum,
-                                                            uint32_t* __restrict__ temp)
+                                                            uint32_t* __restrict__ temp, KeyCodec<Key> codec = KeyCodec<Key>{})
 {
     using L = TileSortLayout<Key, THREADS, KPT>;
     constexpr int KD = L::KD;
@@ -48,7 +50,8 @@ __global__ __launch_bounds__(THREADS) void tile_sort_kernel(const Key* in, Key* 
     uint32_t* wtot = cnt + L::CNT_DW;
     uint32_t* dstart = wtot + 16;                // tile-local first slot of every digit (last pass: the table)
     const uint32_t tid = threadIdx.x;
-    const Key pad_key = static_cast<Key>(~flip);  // digit 15 in every pass: pads stay behind every real key
+    // digit 15 in every pass: pads stay behind every real key (CODEC: the key that encodes to all-ones)
+    const Key pad_key = CODEC ? codec_decode(static_cast<Key>(~Key{0}), codec.ea, codec.em) : static_cast<Key>(~flip);
     // dword index of slot s in the image: row s/KPT, KPT keys per row, 4 dwords of padding per row
     auto image_dw = [](uint32_t s) { return s * KD + ((s >> 4) << 2); };
 
@@ -58,6 +61,9 @@ __global__ __launch_bounds__(THREADS) void tile_sort_kernel(const Key* in, Key* 
     for (int i = 0; i < KPT; ++i) {
         const uint32_t li = tid * KPT + i;
         k[i] = li < n ? in[li] : pad_key;
+        if constexpr (CODEC) {
+            k[i] = codec_encode(k[i], codec.ea, codec.em);
+        }
         if constexpr (PAYLOAD) {
             pl[i] = li < n ? pin[li] : 0u;
         }
@@ -168,7 +174,8 @@ __global__ __launch_bounds__(THREADS) void tile_sort_kernel(const Key* in, Key* 
             for (int r = 0; r < KPT; ++r) {
                 const uint32_t i = static_cast<uint32_t>(r) * THREADS + tid;
                 if (i < n) {
-                    out[i] = *reinterpret_cast<const Key*>(xbuf + image_dw(i));
+                    const Key y = *reinterpret_cast<const Key*>(xbuf + image_dw(i));
+                    out[i] = CODEC ? codec_decode(y, codec.da, codec.dm) : y;
                 }
             }
         }

@@ -220,6 +220,10 @@ class ShardedSorter:
             raise ValueError("a torch.distributed module (or a stand-in with its calls) is required for world_size > 1")
         if not 0 <= rank < world_size:
             raise ValueError(f"rank {rank} outside world of {world_size}")
+        # float keys and descending order are not sharded yet: refused here, before any collective, on every rank alike (a rank
+        # that raised alone later would leave the others waiting in a collective)
+        if getattr(engine, "codec", False):
+            raise ValueError("the sharded sort takes integer keys in ascending order (float and descending engines are refused)")
         self.engine = engine
         self.rank = rank
         self.world = world_size

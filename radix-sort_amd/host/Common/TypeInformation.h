@@ -13,3 +13,5 @@ template <> struct TypeNameString<std::int32_t> { static constexpr std::string_v
 template <> struct TypeNameString<std::uint32_t> { static constexpr std::string_view stdint_name = "uint32_t"; };
 template <> struct TypeNameString<std::int64_t> { static constexpr std::string_view stdint_name = "int64_t"; };
 template <> struct TypeNameString<std::uint64_t> { static constexpr std::string_view stdint_name = "uint64_t"; };
+template <> struct TypeNameString<float> { static constexpr std::string_view stdint_name = "float"; };
+template <> struct TypeNameString<double> { static constexpr std::string_view stdint_name = "double"; };

@@ -8,8 +8,9 @@
 
 namespace {
 
+// rsx_create's key kind: floating-point keys are RSX_KEY_FLOAT (std::is_signed_v is true for them too)
 template <typename T>
-constexpr int key_is_signed = std::is_signed_v<T> ? 1 : 0;
+constexpr int key_kind = std::is_floating_point_v<T> ? RSX_KEY_FLOAT : std::is_signed_v<T> ? RSX_KEY_SIGNED : RSX_KEY_UNSIGNED;
 
 void accumulate(Statistics& dst, const rsx_phase_stat& src)
 {
@@ -47,7 +48,7 @@ OperationStatus RadixSortGPU<DataType>::initialize(hipc::Device Device, hipc::Co
     if (!mHostSpans.m_hKeys.data() || !mHostSpans.m_hResultFromGPU.data()) return S::HOST_BUFFERS_FAILED;
     if (mWithPermutation && !mHostSpans.h_Permut.data()) return S::HOST_BUFFERS_FAILED;
 
-    const int rc = rsx_create(&mEngine, Device.ordinal, static_cast<int>(sizeof(DataType)), key_is_signed<DataType>,
+    const int rc = rsx_create(&mEngine, Device.ordinal, static_cast<int>(sizeof(DataType)), key_kind<DataType>,
                               mWithPermutation ? 1 : 0, mNumberKeysRounded);
     if (rc != RSX_OK) {
         mEngine = nullptr;
@@ -55,7 +56,11 @@ OperationStatus RadixSortGPU<DataType>::initialize(hipc::Device Device, hipc::Co
     }
     rsx_resize(mEngine, mNumberKeysRounded);
     rsx_set_option(mEngine, RSX_OPT_PROFILE, 1);   // RuntimesGPU is always filled, as in the reference
-    rsx_set_option(mEngine, RSX_OPT_REF_DIAGNOSTICS, mRadixBits == 4 ? 1 : 0);   // m_hHistograms / m_hGlobsum in the reference's geometry (4-bit passes only)
+    rsx_set_option(mEngine, RSX_OPT_REF_DIAGNOSTICS, diagnosticTables() ? 1 : 0);   // m_hHistograms / m_hGlobsum in the reference's geometry (4-bit passes only)
+    if (mDescending && rsx_set_option(mEngine, RSX_OPT_DESCENDING, 1) != RSX_OK) {
+        release();
+        return S::INITIALIZATION_FAILED;
+    }
     if (mRadixBits != 4 && rsx_set_option(mEngine, RSX_OPT_RADIX_BITS, mRadixBits) != RSX_OK) {
         release();
         return S::INITIALIZATION_FAILED;
@@ -145,8 +150,9 @@ void RadixSortGPU<DataType>::CopyDataFromDevice(hipc::CommandQueue)
     // (_NUM_HISTOSPLIT words) — src/RadixSortGPU.cpp:390-429.  The engine recomputes both in the
     // reference's geometry (RSX_OPT_REF_DIAGNOSTICS); nothing consumes them, they are for parity.
     // With 8-bit digits (setRadixBits(8)) no pass of the sort is the reference's last 4-bit pass, so its two tables do not exist:
-    // they are not asked for (the engine refuses to hand out tables the last sort did not produce) and are left zeroed.
-    const bool tables = mRadixBits == 4;
+    // they are not asked for (the engine refuses to hand out tables the last sort did not produce) and are left zeroed.  Nor for
+    // float keys or descending order: the engine sorts encoded keys, which have no counterpart in the reference.
+    const bool tables = diagnosticTables();
     if (!tables) {
         std::fill(mHostSpans.m_hHistograms.begin(), mHostSpans.m_hHistograms.end(), 0u);
         std::fill(mHostSpans.m_hGlobsum.begin(), mHostSpans.m_hGlobsum.end(), 0u);
@@ -306,3 +312,5 @@ template class RadixSortGPU<std::int32_t>;
 template class RadixSortGPU<std::int64_t>;
 template class RadixSortGPU<std::uint32_t>;
 template class RadixSortGPU<std::uint64_t>;
+template class RadixSortGPU<float>;
+template class RadixSortGPU<double>;

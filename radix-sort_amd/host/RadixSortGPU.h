@@ -13,6 +13,7 @@
 //     followed by a stream sync and timed with the host stopwatch — the reference's own
 //     accounting (src/RadixSortGPU.cpp:38-56,89-108,128-147,171-190,242-255).
 #pragma once
+#include <type_traits>
 #include <vector>
 
 #include "Common/ComputeState.h"
@@ -62,6 +63,9 @@ public:
     /// Digit width of calculate()'s fused pass loop: 4 (the reference's _NUM_BITS_PER_RADIX, src/Parameters.h:25) or 8 (half the
     /// passes; same result).  The stepwise launchers and the diagnostic read-backs stay those of 4-bit passes.  Call before initialize().
     void setRadixBits(int bits) noexcept { mRadixBits = bits; }
+    /// Descending order (RSX_OPT_DESCENDING), stable: equal keys keep their input order.  Float keys (RadixSortGPU<float> /
+    /// <double>) sort in IEEE 754 totalOrder, see include/radixsort_hip.h.  Call before initialize().
+    void setDescending(bool on) noexcept { mDescending = on; }
     /// Page-lock the key / result (and permutation) spans for the engine's lifetime so that
     /// uploadData / downloadData DMA directly (the CL_MEM_USE_HOST_PTR idea the reference notes
     /// at src/ComputeDeviceData.cpp:26).  Call before initialize().
@@ -91,6 +95,8 @@ private:
     void CopyDataFromDevice(hipc::CommandQueue CommandQueue);
     bool bindQueue(hipc::CommandQueue CommandQueue);
     void foldEventTimings();
+    /// the reference-geometry read-backs exist for ascending integer sorts of 4-bit passes only
+    bool diagnosticTables() const noexcept { return mRadixBits == 4 && !mDescending && !std::is_floating_point_v<DataType>; }
 
     rsx_engine* mEngine{nullptr};            ///< the reference's shared_ptr<ComputeDeviceData>
     HostSpans<DataType> mHostSpans{};
@@ -101,6 +107,7 @@ private:
     bool mWithPermutation{false};
     bool mStepwise{false};
     int mRadixBits{4};
+    bool mDescending{false};
     bool mPinHost{false};
     bool mPinned{false};
     std::vector<void*> mExtraPinned{};
