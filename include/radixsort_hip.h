@@ -315,6 +315,27 @@ int rsx_sort_from_to(rsx_engine* e, const void* d_keys, const uint32_t* d_payloa
  *   (RSX_CALCULATION_FAILED otherwise; n <= capacity gives RSX_RESIZE_FAILED first). */
 int rsx_segmented_sort(rsx_engine* e, const void* d_keys, const uint32_t* d_payload, uint64_t n, const uint64_t* d_offsets, uint64_t num_segments,
                        void* d_keys_out, uint32_t* d_payload_out);
+/* rsx_segmented_topk: the k first keys of every segment's stable sort, by radix select.  Segment s = [off[s], off[s+1]) of length L
+ *   gives m = min(k, L) keys to d_keys_out[s*k .. s*k+m) and their positions relative to off[s], as uint32, to d_index_out[s*k .. s*k+m):
+ *   the first m entries of the stable sort of the segment in the engine's direction.  An ascending engine yields the k smallest keys,
+ *   a descending one (RSX_OPT_DESCENDING) the k largest; equal keys are taken lowest index first, and the result is bitwise the same
+ *   from run to run.  Float keys follow IEEE 754 totalOrder (+NaN above +inf, as torch.topk puts NaN); the only differences from
+ *   torch.topk / torch.sort are -0.0 (below +0.0 here) and negative-sign NaNs (below -inf here).
+ *   Slots [s*k+m, s*k+k), the slots of invalid segments and everything past num_segments*k are not written.
+ *   1 <= k <= 4096 (one LDS tile): a larger k is refused with RSX_CALCULATION_FAILED (sort the segments instead and keep a prefix).
+ *   k == 0, n == 0 or num_segments == 0 returns RSX_OK and launches nothing.
+ *   Key kind and direction follow the engine; the payload flag does not apply (the index output takes its place).
+ *   Buffers: n <= capacity (RSX_RESIZE_FAILED) and n <= 2^31; d_keys 16-byte aligned, d_offsets 8-byte aligned, the outputs need only
+ *   their element alignment.  Any overlap of inputs, outputs and the engine's own buffers is refused with RSX_HOST_BUFFERS_FAILED;
+ *   afterwards rsx_download / rsx_copy_result behave as after rsx_segmented_sort.
+ *   As rsx_segmented_sort: d_offsets is DEVICE memory (num_segments + 1 uint64), the call is asynchronous on the engine's stream and
+ *   never reads the offsets back, every launch is sized from n, num_segments and k.  Segments of at most 4096 keys are sorted in LDS
+ *   by one workgroup each; larger ones take 8-bit select rounds over their tiles (4 for 32-bit keys, 8 for 64-bit), a compaction of
+ *   k candidates per segment and an LDS sort of those.  A segment with off[s+1] < off[s] or off[s+1] > n is neither read nor written,
+ *   and the next rsx_sync / rsx_check_status reports it once (RSX_CALCULATION_FAILED, rsx_last_error names it).  Scratch grows on
+ *   first use of a larger n or num_segments, never inside a stream capture. */
+int rsx_segmented_topk(rsx_engine* e, const void* d_keys, uint64_t n, const uint64_t* d_offsets, uint64_t num_segments, uint32_t k, void* d_keys_out,
+                       uint32_t* d_index_out);
 /* Receive buffers other ranks can write to (the peer-store exchange below): rsx_peer_alloc (hipMalloc + an IPC handle to hand to the other
  * PROCESSES, which map it with rsx_peer_open / rsx_peer_close — peer access over xGMI); ranks that are threads of one process use the
  * pointer itself (after rsx_peer_enable, once per other device). */

@@ -46,7 +46,7 @@ SYMBOLS = [
     "rsx_create", "rsx_destroy", "rsx_set_stream", "rsx_get_stream", "rsx_set_option", "rsx_get_geometry", "rsx_resize",
     "rsx_upload", "rsx_fill_pad", "rsx_download", "rsx_pin_host", "rsx_unpin_host", "rsx_pipeline_submit", "rsx_pipeline_wait", "rsx_host_device_pointer",
     "rsx_histogram", "rsx_scan", "rsx_paste", "rsx_reorder", "rsx_sort", "rsx_sync", "rsx_check_status",
-    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
+    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
 ]
 
 
@@ -152,6 +152,7 @@ def load_library() -> C.CDLL:
         "rsx_peer_enable": ([P, I], I),
         "rsx_sort_from_to": ([P, P, P, U64, I, I, P, P], I),
         "rsx_segmented_sort": ([P, P, P, U64, P, U64, P, P], I),
+        "rsx_segmented_topk": ([P, P, U64, P, U64, C.c_uint32, P, P], I),
         "rsx_msd_count": ([P, P, U64, I, I, P], I),
         "rsx_msd_scatter": ([P, P, P, U64, P, P], I),
         "rsx_msd_plan": ([P, P, C.c_uint32, C.c_uint32, I, I, P], I),
@@ -441,6 +442,14 @@ class Engine:
             self._h, C.c_void_p(d_keys), C.c_void_p(d_payload) if d_payload else None, n, C.c_void_p(d_offsets), num_segments,
             C.c_void_p(d_keys_out), C.c_void_p(d_payload_out) if d_payload_out else None), "rsx_segmented_sort")
 
+    def segmented_topk(self, d_keys: int, n: int, d_offsets: int, num_segments: int, k: int, d_keys_out: int, d_index_out: int) -> None:
+        """The first min(k, L) entries of the stable sort of every segment [off[s], off[s+1]) (L keys) to d_keys_out[s*k ..] and their
+        positions relative to off[s] (uint32) to d_index_out[s*k ..]; other slots are not written.  1 <= k <= 4096 (k == 0: nothing).
+        Asynchronous on the engine's stream; bad offsets are reported by the next sync() / check_status()."""
+        self._check(self.lib.rsx_segmented_topk(
+            self._h, C.c_void_p(d_keys), n, C.c_void_p(d_offsets), num_segments, k, C.c_void_p(d_keys_out), C.c_void_p(d_index_out)),
+            "rsx_segmented_topk")
+
     # -- exchange step of the sharded sort on the top B <= 8 bits ----------------
     def msd_count(self, d_keys: int, n: int, bits: int, world: int, d_counts: int) -> None:
         """Keys per bucket of the top `bits` bits into device memory (256 x uint64 at d_counts, natural order), asynchronously."""
@@ -610,3 +619,85 @@ def sort_rows(x, descending: bool = False):
     col = torch.arange(cols, device=x.device, dtype=torch.int64).to(torch.int32).repeat(rows)      # uint32 bits (cols may reach 2^31)
     values, idx = segmented_sort(flat, offsets, col, descending=descending)
     return values.reshape(rows, cols), (idx.to(torch.int64) & 0xFFFFFFFF).reshape(rows, cols)      # the uint32 payload, unsigned
+
+
+# -- top-k on torch tensors ---------------------------------------------------------------------------------------------------------
+TOPK_MAX_K = 4096       # rsx_segmented_topk's bound: one LDS tile
+
+
+def segmented_topk(keys, offsets, k: int, largest: bool = True):
+    """The k largest (largest=True) or smallest entries of every segment [offsets[s], offsets[s+1]) of the 1-D device tensor `keys` in ONE
+    engine call (rsx_segmented_topk, 1 <= k <= 4096).  offsets: int64 device tensor of num_segments + 1 non-negative entries.
+    Returns (values [S, k], indices [S, k] int64), sorted best first, ties lowest index first, indices relative to the segment start.
+    Slots past a segment's length hold value 0 and index -1.  Float keys follow IEEE 754 totalOrder (+NaN above +inf; -0.0 below +0.0,
+    negative-sign NaNs below -inf).  Bad offsets raise at the engine's next synchronisation (this call does not read them); their rows
+    hold 0 / -1."""
+    import torch
+    if keys.dim() != 1 or not keys.is_cuda:
+        raise ValueError("segmented_topk: keys must be a 1-D device tensor")
+    name = str(keys.dtype).replace("torch.", "")
+    if name not in _KEY_DTYPES:
+        raise TypeError(f"segmented_topk: unsupported key type {keys.dtype}")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.device != keys.device:
+        raise ValueError("segmented_topk: offsets must be a 1-D int64 tensor on the keys' device")
+    k = int(k)
+    if k < 0 or k > TOPK_MAX_K:
+        raise ValueError(f"segmented_topk: k must be in [0, {TOPK_MAX_K}] (sort_rows / segmented_sort and a slice for larger k)")
+    n = keys.numel()
+    nseg = max(offsets.numel() - 1, 0)
+    values = torch.zeros((nseg, k), dtype=keys.dtype, device=keys.device)
+    idx = torch.full((nseg, k), -1, dtype=torch.int32, device=keys.device)     # the uint32 output's bits: -1 marks an unwritten slot
+    if n == 0 or nseg == 0 or k == 0:
+        return values, idx.to(torch.int64)
+    k_in = _aligned_copy(keys, torch)
+    off = offsets if offsets.is_contiguous() and offsets.data_ptr() % 8 == 0 else offsets.clone(memory_format=torch.contiguous_format)
+    device = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    stream = torch.cuda.current_stream(keys.device).cuda_stream
+    eng = _segmented_engine(device, stream, name, False, bool(largest), n)      # largest: a descending engine
+    eng.segmented_topk(k_in.data_ptr(), n, off.data_ptr(), nseg, k, values.data_ptr(), idx.data_ptr())
+    eng.check_status()      # reports bad offsets of calls that have already finished
+    return values, idx.to(torch.int64)      # uint32 positions below 2^31 (n <= 2^31): non-negative as int32
+
+
+def topk(x, k: int, dim: int = -1, largest: bool = True, sorted: bool = True):
+    """torch.topk(x, k, dim, largest) on a device tensor: (values, indices int64) shaped like torch.topk's, always sorted (best first,
+    equal values lowest index first; sorted=False is accepted).  Every row along `dim` is one segment of ONE rsx_segmented_topk call.
+    Values equal torch.topk's for integer dtypes and for floats without -0.0 and negative-sign NaNs (float keys follow IEEE 754
+    totalOrder here); indices equal the first k of torch.sort(stable=True)'s.  For k > 4096 this falls back to sort_rows (one
+    segmented sort) and a slice.  Supported dtypes: int32, uint32, int64, uint64, float32, float64 (TypeError otherwise)."""
+    import torch
+    if not x.is_cuda:
+        raise ValueError("topk: x must be a device tensor")
+    name = str(x.dtype).replace("torch.", "")
+    if name not in _KEY_DTYPES:
+        raise TypeError(f"topk: unsupported dtype {x.dtype}")
+    del sorted                                                  # the output is always sorted
+    squeeze = x.dim() == 0          # torch.topk of a 0-d tensor: one row of one element, 0-d results
+    if squeeze:
+        x = x.reshape(1)
+    dim = dim % x.dim()
+    size = x.shape[dim]
+    k = int(k)
+    if k < 0 or k > size:
+        raise ValueError(f"topk: k = {k} is out of range for dimension {dim} of size {size}")
+    xm = x.movedim(dim, -1)
+    out_shape = xm.shape[:-1] + (k,)
+    rows = xm.numel() // size if size else 0
+    if k == 0 or rows == 0:
+        v = torch.empty(out_shape, dtype=x.dtype, device=x.device)
+        i = torch.empty(out_shape, dtype=torch.int64, device=x.device)
+    else:
+        flat = xm.contiguous().reshape(rows, size)
+        if k > TOPK_MAX_K:
+            sv, si = sort_rows(flat, descending=largest)
+            v, i = sv[:, :k].contiguous(), si[:, :k].contiguous()
+        else:
+            if rows * size > (1 << 31):
+                raise ValueError("topk: at most 2^31 elements (rsx_segmented_topk's bound)")
+            offsets = torch.arange(0, rows + 1, device=x.device, dtype=torch.int64) * size
+            v, i = segmented_topk(flat.reshape(-1), offsets, k, largest=largest)
+        v, i = v.reshape(out_shape), i.reshape(out_shape)
+    v, i = v.movedim(-1, dim), i.movedim(-1, dim)
+    if squeeze and k == 1:
+        v, i = v.reshape(()), i.reshape(())
+    return v, i

@@ -13,6 +13,7 @@
 #endif
 #include "rsx_kernels.hpp"
 #include "rsx_segmented.hpp"
+#include "rsx_topk.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -209,6 +210,11 @@ struct rsx_engine {
     uint32_t* seg_gsum = nullptr;               // its scan's group sums, raw and scanned
     uint32_t* seg_gsum2 = nullptr;
     uint64_t seg_bsum_cap = 0, seg_list_cap = 0, seg_large_cap = 0, seg_tstart_cap = 0, seg_table_cap = 0, seg_gsum_cap = 0, seg_gsum2_cap = 0;
+    // rsx_segmented_topk (capi_topk.inc): the segmented sort's scratch above, plus (grown the same way)
+    rsx::TopkState* topk_state = nullptr;       // select state of every large segment
+    uint32_t* topk_start = nullptr;             // [large segment][256]: counts of the group tiles a segment begins in
+    uint32_t* topk_cont = nullptr;              // [group][256]: counts of the segment a group of tiles continues
+    uint64_t topk_state_cap = 0, topk_start_cap = 0, topk_cont_cap = 0;
 
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -1259,7 +1265,7 @@ int check_scan_timeout(rsx_engine* e, int status)
         const uint32_t v = *bad;
         if (v != 0) {
             *bad = 0;
-            return fail(status, ("rsx_segmented_sort: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; it was neither read nor "
+            return fail(status, ("rsx_segmented_sort / rsx_segmented_topk: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; it was neither read nor "
                                  "written (the first such segment of the call; reported once; the engine remains usable)").c_str());
         }
     }
@@ -1632,7 +1638,8 @@ int rsx_destroy(rsx_engine* e)
     if (e->msd_plan && hipFree(e->msd_plan) != hipSuccess) status = RSX_CLEANUP_FAILED;
     for (void* p : {static_cast<void*>(e->seg_hdr), static_cast<void*>(e->seg_temp), static_cast<void*>(e->seg_bsum), static_cast<void*>(e->seg_list),
                     static_cast<void*>(e->seg_large), static_cast<void*>(e->seg_tstart), static_cast<void*>(e->seg_table), static_cast<void*>(e->seg_gsum),
-                    static_cast<void*>(e->seg_gsum2)}) {
+                    static_cast<void*>(e->seg_gsum2), static_cast<void*>(e->topk_state), static_cast<void*>(e->topk_start),
+                    static_cast<void*>(e->topk_cont)}) {
         if (p && hipFree(p) != hipSuccess) status = RSX_CLEANUP_FAILED;
     }
     if (e->seg_status_host && hipHostFree(e->seg_status_host) != hipSuccess) status = RSX_CLEANUP_FAILED;
@@ -2376,6 +2383,7 @@ int rsx_peer_enable(rsx_engine* e, int peer_device)
 
 #include "capi_msd.inc"
 #include "capi_segmented.inc"
+#include "capi_topk.inc"
 
 int rsx_key_range(rsx_engine* e, const void* d_keys, uint64_t n, uint64_t* lo, uint64_t* hi)
 {

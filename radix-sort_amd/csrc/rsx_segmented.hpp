@@ -43,7 +43,7 @@ struct SegHeader {
 struct SegLarge {
     uint64_t a, b;                   // [a, b)
     uint64_t dest;                   // a - (keys of the large segments before this one), modulo 2^64: slot = dest + scanned table entry + rank in digit
-    uint64_t pad;
+    uint64_t pad;                    // the segment's index for rsx_segmented_topk, else 0
 };
 
 __device__ __forceinline__ uint32_t seg_class(uint64_t len)
@@ -95,7 +95,8 @@ __device__ __forceinline__ void block_scan_u64(uint64_t (&v)[F], uint64_t (&tot)
 // WRITE = false: block sums of the fields into bsum[block][SF_STRIDE] (SF_BAD: the block's first bad segment, ~0 if none).
 // WRITE = true: bsum holds the scanned block prefixes (seg_scan_kernel); every segment takes its place: small classes -> list,
 // large segments -> large[] / tstart[] (only when the header says the chain's bounds hold), one-key segments are copied.
-template <typename Key, bool WRITE>
+// IDS = true (rsx_segmented_topk): each large segment's index goes to SegLarge::pad and one-key segments are left to the caller.
+template <typename Key, bool WRITE, bool IDS = false>
 __global__ __launch_bounds__(kSegClassifyThreads) void seg_classify_kernel(const uint64_t* __restrict__ off, uint64_t nseg, uint64_t n,
                                                                            uint64_t* __restrict__ bsum, const SegHeader* __restrict__ hdr,
                                                                            uint32_t* __restrict__ list, SegLarge* __restrict__ large,
@@ -156,9 +157,11 @@ __global__ __launch_bounds__(kSegClassifyThreads) void seg_classify_kernel(const
             if (b < a || b > n) continue;
             const uint64_t len = b - a;
             if (len == 1) {
-                kout[a] = kin[a];
-                if (pout) {
-                    pout[a] = pin[a];
+                if constexpr (!IDS) {
+                    kout[a] = kin[a];
+                    if (pout) {
+                        pout[a] = pin[a];
+                    }
                 }
                 continue;
             }
@@ -170,7 +173,7 @@ __global__ __launch_bounds__(kSegClassifyThreads) void seg_classify_kernel(const
             } else {
                 if (chain) {
                     const uint64_t j = f[SF_LARGE];
-                    large[j] = SegLarge{a, b, a - f[SF_KEYS], 0};
+                    large[j] = SegLarge{a, b, a - f[SF_KEYS], IDS ? s : 0};
                     tstart[j] = static_cast<uint32_t>(f[SF_TILES]);
                 }
                 f[SF_LARGE] += 1;
