@@ -8,6 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import _topk_ref
+from test_gpu_float_keys import UINT, enc
 from test_gpu_topk import topk_oracle
 from test_segmented import HEADER
 
@@ -77,3 +79,101 @@ def test_no_cpu_path(rsx):
         with pytest.raises(rsx.RadixSortError) as ei:
             rsx.Engine(np.uint32, 16).segmented_topk(0, 16, 0, 1, 4, 0, 0)
         assert ei.value.status == 2              # INITIALIZATION_FAILED: no device
+
+
+# -- the linear-time reference of the production-shape tests (tests/_topk_ref.py) ---------------------------------------------------
+
+def _ragged_case(rng, dtype, kind):
+    from test_gpu_float_keys import random_bits, special
+    from test_gpu_segmented import offsets_from
+    lens = [0, 1, 2, 5, 40, 255, 256, 257, 300, 1000, 1025, 3000, 4097, 9000, 0, 17]
+    off = offsets_from(list(rng.permutation(lens)), start=int(rng.integers(0, 4)))
+    n = int(off[-1]) + 3
+    if kind == "random":
+        x = random_bits(dtype, n, rng)
+        x[rng.integers(0, n, n // 3)] = x[rng.integers(0, n, n // 3)]                    # ties
+    elif kind == "few":
+        x = rng.integers(0, 3, n).astype(UINT[np.dtype(dtype)]).view(dtype)          # ties across every k boundary
+    elif kind == "equal":
+        x = np.full(n, 7, dtype=UINT[np.dtype(dtype)]).view(dtype)
+    elif kind == "special":
+        x = special(dtype, n, rng)                                                       # ±0, ±inf, NaNs of both signs with payloads
+    else:
+        x = _topk_ref.digit_local(dtype, off, n, rng, kind, bool(rng.integers(0, 2)), k=300)
+    return x, off
+
+
+KEY_TYPES = [np.uint32, np.int32, np.float32, np.uint64, np.int64, np.float64]
+REF_CASES = [(d, kind) for d in KEY_TYPES for kind in ["random", "few", "equal", "special", "window", "low", "straddle"]
+             if kind != "special" or np.dtype(d).kind == "f"]
+
+
+@pytest.mark.parametrize("dtype,kind", REF_CASES, ids=[f"{np.dtype(d).name}-{kind}" for d, kind in REF_CASES])
+def test_fast_reference_equals_oracle(dtype, kind):
+    rng = np.random.default_rng(REF_CASES.index((dtype, kind)))
+    x, off = _ragged_case(rng, dtype, kind)
+    bad = np.concatenate([off, [off[-1] - 3, off[-1] + 10]]).astype(np.uint64)      # a decreasing and a past-n segment at the end
+    for o in (off, bad):
+        for desc in (False, True):
+            ref = _topk_ref.fast_topk(x, o, 1100, desc)
+            for k in (1, 2, 300, 1024, 1100):
+                wk, wi, written = topk_oracle(x, o, k, desc)
+                gk, gi, gw = ref.at(k)
+                assert np.array_equal(gw, written)
+                assert np.array_equal(np.where(written, gk, 0), wk) and np.array_equal(np.where(written, gi, 0), wi), (k, desc)
+
+
+@pytest.mark.parametrize("dtype", KEY_TYPES, ids=lambda d: np.dtype(d).name)
+def test_order_words_decode(dtype):
+    """dec inverts the engine's encoding, and the builders' order words land where they should: the pad-heavy keys are the pad key
+    (encoded all ones in the call's order), digit-local keys differ from their segment's first key in one round's byte only."""
+    rng = np.random.default_rng(3)
+    u = UINT[np.dtype(dtype)]
+    e = rng.integers(0, np.iinfo(u).max, 5000, dtype=u, endpoint=True)
+    e[:4] = [0, 1, np.iinfo(u).max, np.iinfo(u).max >> 1]
+    assert np.array_equal(enc(_topk_ref.dec(e, dtype)), e)
+    ones = np.iinfo(u).max
+    pad_asc = {"uint32": ones, "uint64": ones, "int32": 0x7FFFFFFF, "int64": 0x7FFFFFFFFFFFFFFF, "float32": 0x7FFFFFFF,
+               "float64": 0x7FFFFFFFFFFFFFFF}[np.dtype(dtype).name]
+    pad_desc = {"uint32": 0, "uint64": 0, "int32": 0x80000000, "int64": 0x8000000000000000, "float32": 0xFFFFFFFF,
+                "float64": 0xFFFFFFFFFFFFFFFF}[np.dtype(dtype).name]
+    off = np.array([0, 300, 5000], dtype=np.uint64)
+    for desc, pad in ((False, pad_asc), (True, pad_desc)):
+        x = _topk_ref.pad_heavy(dtype, off, 5000, rng, desc).view(u)
+        assert np.count_nonzero(x == u(pad)) > 0.9 * 5000
+        for variant in ("window", "low"):
+            x = _topk_ref.digit_local(dtype, off, 5000, rng, variant, desc)
+            o = enc(x)
+            o = ~o if desc else o
+            diff = int(np.bitwise_or.reduce(o[300:5000] ^ o[300]))       # the one large segment: round 0, or the lowest byte
+            bits = np.dtype(u).itemsize * 8
+            assert diff == (0xFF << (bits - 8) if variant == "window" else 0xFF)
+
+
+def test_shapes_reach_their_paths():
+    """Each production-shape layout of tests/test_gpu_topk_shapes.py still reaches what it is there for on 256 CUs (the mirror of
+    seg_shape and topk_group_tiles in tests/_topk_ref.py; if those formulas change, this fails first)."""
+    geo = {}
+    for name, (_, make) in _topk_ref.SHAPES.items():
+        off = make()
+        geo[name] = _topk_ref.select_geometry(off, _topk_ref.shape_n(off))
+    for name, g in geo.items():          # every shape: groups of several tiles, segments that begin inside a group
+        assert g["gtiles"] >= 2 and g["switches"] > 0, (name, g)
+    assert geo["1024x50257_f32"]["gtiles"] == 7 and geo["1024x50257_f32"]["switches"] == 879
+    assert geo["1024x50257_f32"]["nlarge"] > 512                        # the pick kernel strides over segments
+    g = geo["2048x5000_u64"]
+    assert g["nlarge"] > 1024 and g["switches"] == 1365                 # ... and the final sort at k > 1024 (k = 4096 runs)
+    assert g["tiles"] / g["nlarge"] < g["gtiles"]                       # groups hold two segment starts
+    assert max(_topk_ref.SHAPE_KS) > 1024
+    g = geo["64x151936_i64"]
+    assert (151936 % _topk_ref.TILE) != 0 and g["tiles"] > 64 * 37 and g["switches"] > 0            # unaligned rows over 37 / 38 tiles
+    off = _topk_ref.SHAPES["ragged_i32"][1]()
+    lens = np.diff(off.astype(np.int64))
+    assert off[0] % 2 == 1 and lens.max() <= 40000 and (lens[lens > 4096] >= 4097).all() and (lens <= 4096).any()
+    # the vocabulary shapes of the torch-helper test
+    g = _topk_ref.select_geometry(_topk_ref.rows(4096, 32000), 4096 * 32000)
+    assert g["gtiles"] == 18 and g["switches"] == 3812
+    g = _topk_ref.select_geometry(_topk_ref.rows(512, 50257), 512 * 50257)
+    assert g["gtiles"] >= 2 and g["switches"] > 0
+    # and the old top-k tests never did: the widest, 64 x 2^17, has no segment start inside a group
+    assert _topk_ref.select_geometry(_topk_ref.rows(64, 1 << 17), 64 << 17)["switches"] == 0
