@@ -336,6 +336,34 @@ int rsx_segmented_sort(rsx_engine* e, const void* d_keys, const uint32_t* d_payl
  *   first use of a larger n or num_segments, never inside a stream capture. */
 int rsx_segmented_topk(rsx_engine* e, const void* d_keys, uint64_t n, const uint64_t* d_offsets, uint64_t num_segments, uint32_t k, void* d_keys_out,
                        uint32_t* d_index_out);
+/* rsx_segmented_select: the entries at given ranks of every segment's stable sort (k-th value, median, quantiles), by radix select.
+ *   For segment s = [off[s], off[s+1]) of length L and every q < R (R = ranks_per_segment), with r = d_ranks[s*R + q]:
+ *   r < L:  d_keys_out[s*R + q] is the key at position r of the stable sort of the segment in the engine's direction, bit pattern
+ *           unchanged, and d_index_out[s*R + q] that element's position relative to off[s], as uint32: entry r of what
+ *           rsx_segmented_sort with an iota payload gives for the segment.  Among equal keys this is the (r - #strictly better + 1)-th
+ *           one in index order, for ascending and descending (RSX_OPT_DESCENDING) engines alike; the result is bitwise the same
+ *           from run to run.
+ *   r >= L: (0xFFFFFFFF is the conventional "none"; an empty segment has no valid rank) the slot is not written, so ragged segments
+ *           can share one R.  The slots of invalid segments and everything past num_segments*R are not written either.
+ *   The ranks of a segment may repeat and need not be ordered; they are not limited to 4096 as the top-k's k is.
+ *   Float keys follow IEEE 754 totalOrder (+NaN above +inf, as torch.kthvalue / torch.median put NaN); the only differences from
+ *   torch are -0.0 (below +0.0 here) and negative-sign NaNs (below -inf here).
+ *   1 <= R <= 8 (8 histograms per wave fill the LDS budget of a select round): a larger R is refused with RSX_CALCULATION_FAILED
+ *   (call again for further ranks, or sort the segments instead).  R == 0, n == 0 or num_segments == 0 returns RSX_OK and launches nothing.
+ *   Key kind and direction follow the engine; the payload flag does not apply (the index output takes its place).
+ *   Buffers: n <= capacity (RSX_RESIZE_FAILED) and n <= 2^31; d_keys 16-byte aligned, d_offsets 8-byte aligned, d_ranks 4-byte
+ *   aligned, the outputs need only their element alignment.  Any overlap of inputs, outputs and the engine's own buffers is refused
+ *   with RSX_HOST_BUFFERS_FAILED; afterwards rsx_download / rsx_copy_result behave as after rsx_segmented_sort.
+ *   As rsx_segmented_topk: d_offsets (num_segments + 1 uint64) and d_ranks (num_segments * R uint32) are DEVICE memory, the call is
+ *   asynchronous on the engine's stream and never reads them back, every launch is sized from n, num_segments and R.  Segments of at
+ *   most 4096 keys are sorted in LDS by one workgroup each; larger ones take 8-bit select rounds over their tiles (4 for 32-bit keys,
+ *   8 for 64-bit) in which ONE pass over the keys serves all R ranks, then a count of the ties of every rank's key per tile and a pass
+ *   that locates the wanted tie: rounds + 2 readings of the keys whatever R is, and nothing the size of the input is written.
+ *   A segment with off[s+1] < off[s] or off[s+1] > n is neither read nor written, and the next rsx_sync / rsx_check_status reports it
+ *   once (RSX_CALCULATION_FAILED, rsx_last_error names it).  Scratch grows on first use of a larger n, num_segments or R, never inside
+ *   a stream capture. */
+int rsx_segmented_select(rsx_engine* e, const void* d_keys, uint64_t n, const uint64_t* d_offsets, uint64_t num_segments, const uint32_t* d_ranks,
+                         uint32_t ranks_per_segment, void* d_keys_out, uint32_t* d_index_out);
 /* Receive buffers other ranks can write to (the peer-store exchange below): rsx_peer_alloc (hipMalloc + an IPC handle to hand to the other
  * PROCESSES, which map it with rsx_peer_open / rsx_peer_close — peer access over xGMI); ranks that are threads of one process use the
  * pointer itself (after rsx_peer_enable, once per other device). */

@@ -46,7 +46,7 @@ SYMBOLS = [
     "rsx_create", "rsx_destroy", "rsx_set_stream", "rsx_get_stream", "rsx_set_option", "rsx_get_geometry", "rsx_resize",
     "rsx_upload", "rsx_fill_pad", "rsx_download", "rsx_pin_host", "rsx_unpin_host", "rsx_pipeline_submit", "rsx_pipeline_wait", "rsx_host_device_pointer",
     "rsx_histogram", "rsx_scan", "rsx_paste", "rsx_reorder", "rsx_sort", "rsx_sync", "rsx_check_status",
-    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
+    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
 ]
 
 
@@ -153,6 +153,7 @@ def load_library() -> C.CDLL:
         "rsx_sort_from_to": ([P, P, P, U64, I, I, P, P], I),
         "rsx_segmented_sort": ([P, P, P, U64, P, U64, P, P], I),
         "rsx_segmented_topk": ([P, P, U64, P, U64, C.c_uint32, P, P], I),
+        "rsx_segmented_select": ([P, P, U64, P, U64, P, C.c_uint32, P, P], I),
         "rsx_msd_count": ([P, P, U64, I, I, P], I),
         "rsx_msd_scatter": ([P, P, P, U64, P, P], I),
         "rsx_msd_plan": ([P, P, C.c_uint32, C.c_uint32, I, I, P], I),
@@ -450,6 +451,16 @@ class Engine:
             self._h, C.c_void_p(d_keys), n, C.c_void_p(d_offsets), num_segments, k, C.c_void_p(d_keys_out), C.c_void_p(d_index_out)),
             "rsx_segmented_topk")
 
+    def segmented_select(self, d_keys: int, n: int, d_offsets: int, num_segments: int, d_ranks: int, ranks_per_segment: int,
+                         d_keys_out: int, d_index_out: int) -> None:
+        """For every segment s = [off[s], off[s+1]) (L keys) and q < R = ranks_per_segment, with r = d_ranks[s*R + q] (DEVICE memory,
+        uint32): entry r of the segment's stable sort goes to d_keys_out[s*R + q], its position relative to off[s] (uint32) to
+        d_index_out[s*R + q]; slots with r >= L are not written.  1 <= R <= 8 (R == 0: nothing).  Asynchronous on the engine's stream;
+        bad offsets are reported by the next sync() / check_status()."""
+        self._check(self.lib.rsx_segmented_select(
+            self._h, C.c_void_p(d_keys), n, C.c_void_p(d_offsets), num_segments, C.c_void_p(d_ranks), ranks_per_segment,
+            C.c_void_p(d_keys_out), C.c_void_p(d_index_out)), "rsx_segmented_select")
+
     # -- exchange step of the sharded sort on the top B <= 8 bits ----------------
     def msd_count(self, d_keys: int, n: int, bits: int, world: int, d_counts: int) -> None:
         """Keys per bucket of the top `bits` bits into device memory (256 x uint64 at d_counts, natural order), asynchronously."""
@@ -701,3 +712,199 @@ def topk(x, k: int, dim: int = -1, largest: bool = True, sorted: bool = True):
     if squeeze and k == 1:
         v, i = v.reshape(()), i.reshape(())
     return v, i
+
+
+# -- selection on torch tensors: k-th value, median, quantiles ----------------------------------------------------------------------
+SELECT_MAX_RANKS = 8       # rsx_segmented_select's bound per call; more ranks are served in chunks
+QUANTILE_MODES = ("linear", "lower", "higher", "midpoint", "nearest")
+
+
+def segmented_select(keys, offsets, ranks, descending: bool = False):
+    """Entry ranks[s, q] of the stable sort of every segment [offsets[s], offsets[s+1]) of the 1-D device tensor `keys`, without sorting
+    (rsx_segmented_select; ranks are not limited to 4096 as segmented_topk's k is).  offsets: int64 device tensor of num_segments + 1
+    non-negative entries; ranks: integer device tensor [S, R] or [S], 0-based, in the direction given (descending: rank 0 is the largest).
+    Returns (values [S, R], indices [S, R] int64), indices relative to the segment start.  A rank that is negative or not below its
+    segment's length selects nothing: the slot holds value 0 and index -1.  More than 8 ranks per segment take one engine call per 8.
+    Equal keys rank in index order, so the index of a tie is defined (torch leaves it open).  Float keys follow IEEE 754 totalOrder (+NaN
+    above +inf; -0.0 below +0.0, negative-sign NaNs below -inf).  Bad offsets raise at the engine's next synchronisation (this call does
+    not read them); their rows hold 0 / -1."""
+    import torch
+    if keys.dim() != 1 or not keys.is_cuda:
+        raise ValueError("segmented_select: keys must be a 1-D device tensor")
+    name = str(keys.dtype).replace("torch.", "")
+    if name not in _KEY_DTYPES:
+        raise TypeError(f"segmented_select: unsupported key type {keys.dtype}")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.device != keys.device:
+        raise ValueError("segmented_select: offsets must be a 1-D int64 tensor on the keys' device")
+    nseg = max(offsets.numel() - 1, 0)
+    if ranks.device != keys.device or ranks.is_floating_point() or ranks.dtype == torch.bool or ranks.dim() not in (1, 2) or ranks.shape[0] != nseg:
+        raise ValueError("segmented_select: ranks must be an integer tensor [num_segments, R] or [num_segments] on the keys' device")
+    r64 = ranks.reshape(nseg, -1).to(torch.int64)
+    R = r64.shape[1]
+    n = keys.numel()
+    values = torch.zeros((nseg, R), dtype=keys.dtype, device=keys.device)
+    idx = torch.full((nseg, R), -1, dtype=torch.int32, device=keys.device)     # the uint32 output's bits: -1 marks an unwritten slot
+    if n == 0 or nseg == 0 or R == 0:
+        return values, idx.to(torch.int64)
+    # uint32 bits for the engine; n <= 2^31, so everything outside [0, 2^31) selects nothing anyway: 0xFFFFFFFF
+    r32 = torch.where((r64 < 0) | (r64 >= (1 << 31)), torch.full_like(r64, -1), r64).to(torch.int32)
+    k_in = _aligned_copy(keys, torch)
+    off = offsets if offsets.is_contiguous() and offsets.data_ptr() % 8 == 0 else offsets.clone(memory_format=torch.contiguous_format)
+    device = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    stream = torch.cuda.current_stream(keys.device).cuda_stream
+    eng = _segmented_engine(device, stream, name, False, bool(descending), n)
+    if R <= SELECT_MAX_RANKS:
+        r_in = r32.contiguous()
+        eng.segmented_select(k_in.data_ptr(), n, off.data_ptr(), nseg, r_in.data_ptr(), R, values.data_ptr(), idx.data_ptr())
+    else:
+        for c in range(0, R, SELECT_MAX_RANKS):
+            r_in = r32[:, c:c + SELECT_MAX_RANKS].contiguous()
+            v_c = torch.zeros(r_in.shape, dtype=keys.dtype, device=keys.device)
+            i_c = torch.full(r_in.shape, -1, dtype=torch.int32, device=keys.device)
+            eng.segmented_select(k_in.data_ptr(), n, off.data_ptr(), nseg, r_in.data_ptr(), r_in.shape[1], v_c.data_ptr(), i_c.data_ptr())
+            values[:, c:c + SELECT_MAX_RANKS] = v_c
+            idx[:, c:c + SELECT_MAX_RANKS] = i_c
+    eng.check_status()      # reports bad offsets of calls that have already finished
+    return values, idx.to(torch.int64)      # uint32 positions below 2^31 (n <= 2^31): non-negative as int32
+
+
+def select_ranks(size: int, k=None, q=None, interpolation: str = "linear"):
+    """The rank arithmetic of kthvalue / median / quantile, as a pure function of the row length: (lo, hi, weight) such that the result
+    is lerp(sorted[lo], sorted[hi], weight) on the ascending row.
+      k given (1-based, torch.kthvalue): (k - 1, k - 1, None).
+      neither k nor q (torch.median(x, dim), the lower median): ((size - 1) // 2, same, None).
+      q given (a floating tensor of quantiles in [0, 1], any device; torch.quantile's arithmetic in q's dtype): pos = q * (size - 1);
+        linear: lo = floor(pos), hi = ceil(pos), weight = pos - lo;  midpoint: the same ranks, weight 0.5;  lower / higher / nearest:
+        lo = hi = floor / ceil / round-half-to-even of pos, weight None.  lo and hi are int64 tensors shaped like q, clamped to the row."""
+    size = int(size)
+    if size < 1:
+        raise ValueError("select_ranks: the dimension must not be empty")
+    if k is not None:
+        k = int(k)
+        if k < 1 or k > size:
+            raise ValueError(f"kthvalue: k = {k} is out of range for a dimension of size {size}")
+        return k - 1, k - 1, None
+    if q is None:
+        return (size - 1) // 2, (size - 1) // 2, None
+    import torch
+    if interpolation not in QUANTILE_MODES:
+        raise ValueError(f"quantile: interpolation must be one of {QUANTILE_MODES}, not {interpolation!r}")
+    pos = q * (size - 1)
+    if interpolation == "lower":
+        pos = pos.floor()
+    elif interpolation == "higher":
+        pos = pos.ceil()
+    elif interpolation == "nearest":
+        pos = pos.round()
+    lo = pos.to(torch.int64).clamp(0, size - 1)
+    if interpolation in ("lower", "higher", "nearest"):
+        return lo, lo, None
+    hi = pos.ceil().to(torch.int64).clamp(0, size - 1)
+    weight = torch.full_like(pos, 0.5) if interpolation == "midpoint" else pos - lo
+    return lo, hi, weight
+
+
+def _select_along(what: str, x, dim: int, ranks):
+    """x's rows along `dim` as segments of one segmented_select call each 8 ranks: `ranks` is a list of ints or an int64 tensor [R], the same
+    for every row.  Returns (values, indices) shaped x.movedim(dim, -1).shape[:-1] + (R,), and the normalised dim."""
+    import torch
+    if not x.is_cuda:
+        raise ValueError(f"{what}: x must be a device tensor")
+    name = str(x.dtype).replace("torch.", "")
+    if name not in _KEY_DTYPES:
+        raise TypeError(f"{what}: unsupported dtype {x.dtype}")
+    if x.dim() == 0:
+        x = x.reshape(1)
+    dim = dim % x.dim()
+    size = x.shape[dim]
+    if size == 0:
+        raise ValueError(f"{what}: dimension {dim} is empty")
+    if not torch.is_tensor(ranks):
+        ranks = torch.tensor(list(ranks), dtype=torch.int64).to(x.device, non_blocking=True)
+    xm = x.movedim(dim, -1)
+    rows = xm.numel() // size
+    out_shape = xm.shape[:-1] + (ranks.numel(),)
+    if rows == 0:
+        return torch.empty(out_shape, dtype=x.dtype, device=x.device), torch.empty(out_shape, dtype=torch.int64, device=x.device), dim
+    if rows * size > (1 << 31):
+        raise ValueError(f"{what}: at most 2^31 elements (rsx_segmented_select's bound)")
+    flat = xm.contiguous().reshape(-1)
+    offsets = torch.arange(0, rows + 1, device=x.device, dtype=torch.int64) * size
+    v, i = segmented_select(flat, offsets, ranks.reshape(1, -1).expand(rows, -1), descending=False)
+    return v.reshape(out_shape), i.reshape(out_shape), dim
+
+
+def kthvalue(x, k: int, dim: int = -1, keepdim: bool = False):
+    """torch.kthvalue(x, k, dim, keepdim) on a device tensor: (values, indices int64), the k-th smallest entry (k is 1-based) of every row
+    along `dim`, by radix select in ONE rsx_segmented_select call — no sort, any k up to the row length.  Supported dtypes: int32, uint32,
+    int64, uint64, float32, float64 (TypeError otherwise).  Two differences from torch: among equal values the index is the one a stable
+    sort puts at rank k - 1 (torch leaves it unspecified); float keys follow IEEE 754 totalOrder, so +NaN is the largest key as in
+    torch, but -0.0 < +0.0 and negative-sign NaNs rank below -inf."""
+    scalar = x.dim() == 0
+    size = 1 if scalar else x.shape[dim % x.dim()]
+    r, _, _ = select_ranks(size, k=k) if x.is_cuda and size else (0, 0, None)
+    v, i, dim = _select_along("kthvalue", x, dim, [r])
+    if scalar:
+        return v.reshape(()), i.reshape(())
+    v, i = v.movedim(-1, dim), i.movedim(-1, dim)
+    return (v, i) if keepdim else (v.squeeze(dim), i.squeeze(dim))
+
+
+def median(x, dim: int = -1, keepdim: bool = False):
+    """torch.median(x, dim, keepdim) on a device tensor: (values, indices int64), the lower median (rank (size - 1) // 2 of the ascending
+    row) of every row along `dim`, by radix select in ONE rsx_segmented_select call.  Dtypes and the two differences from torch as
+    kthvalue: tie indices are defined here (stable order); float keys follow totalOrder (+NaN largest as in torch, -0.0 < +0.0,
+    negative-sign NaNs below -inf), so a row's median is NaN only if NaNs reach its middle rank — torch.median returns NaN for any row
+    that holds one."""
+    scalar = x.dim() == 0
+    size = 1 if scalar else x.shape[dim % x.dim()]
+    v, i, dim = _select_along("median", x, dim, [(size - 1) // 2 if size else 0])
+    if scalar:
+        return v.reshape(()), i.reshape(())
+    v, i = v.movedim(-1, dim), i.movedim(-1, dim)
+    return (v, i) if keepdim else (v.squeeze(dim), i.squeeze(dim))
+
+
+def quantile(x, q, dim: int = -1, keepdim: bool = False, interpolation: str = "linear"):
+    """torch.quantile(x, q, dim, keepdim, interpolation=...) on a float32 / float64 device tensor, by radix select: the ranks floor and
+    ceil of q * (size - 1) of every row along `dim` go through one rsx_segmented_select call (8 ranks per call, i.e. 4 interpolated
+    quantiles), and the result is torch.lerp(lo, hi, pos - floor(pos)) (midpoint: weight 0.5; lower / higher / nearest: one rank each,
+    nearest rounding half to even as torch does).  q: a float, a sequence of floats or a 0-D / 1-D tensor in [0, 1] (a device tensor is
+    not read back: its entries are clamped to the row instead of checked).  Shape as torch.quantile: a 1-D q comes first.
+    Differences from torch: float keys follow IEEE 754 totalOrder (+NaN largest, -0.0 < +0.0, negative-sign NaNs below -inf) and NaN is
+    not propagated — a row holding NaNs yields NaN only where a selected rank reaches them."""
+    import torch
+    if not x.is_cuda:
+        raise ValueError("quantile: x must be a device tensor")
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"quantile: unsupported dtype {x.dtype} (float32 and float64)")
+    if interpolation not in QUANTILE_MODES:
+        raise ValueError(f"quantile: interpolation must be one of {QUANTILE_MODES}, not {interpolation!r}")
+    if torch.is_tensor(q):
+        if q.dim() > 1:
+            raise ValueError("quantile: q must be a scalar or 1-D")
+        if not q.is_cuda and q.numel() and not bool(((q >= 0) & (q <= 1)).all()):
+            raise ValueError("quantile: q must be in [0, 1]")
+        qt = q.to(device=x.device, dtype=x.dtype, non_blocking=True)
+    else:
+        ql = [float(v) for v in q] if isinstance(q, (list, tuple)) else float(q)
+        if not all(0.0 <= v <= 1.0 for v in (ql if isinstance(ql, list) else [ql])):
+            raise ValueError("quantile: q must be in [0, 1]")
+        qt = torch.tensor(ql, dtype=x.dtype).to(x.device, non_blocking=True)
+    scalar_q = qt.dim() == 0
+    qt = qt.reshape(-1)
+    nq = qt.numel()
+    xs = x.reshape(1) if x.dim() == 0 else x
+    d = dim % xs.dim()
+    if xs.shape[d] == 0:
+        raise ValueError(f"quantile: dimension {d} is empty")
+    lo, hi, weight = select_ranks(xs.shape[d], q=qt, interpolation=interpolation)
+    ranks = lo if weight is None else torch.cat([lo, hi])
+    v, _, d = _select_along("quantile", xs, d, ranks)
+    out = v[..., :nq] if weight is None else torch.lerp(v[..., :nq], v[..., nq:], weight)
+    out = out.movedim(-1, 0)                       # [Q, rows...]
+    if keepdim:
+        out = out.unsqueeze(d + 1)
+    if x.dim() == 0 and not keepdim:
+        out = out.reshape(nq)
+    return out[0] if scalar_q else out

@@ -14,6 +14,7 @@
 #include "rsx_kernels.hpp"
 #include "rsx_segmented.hpp"
 #include "rsx_topk.hpp"
+#include "rsx_select.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -210,7 +211,8 @@ struct rsx_engine {
     uint32_t* seg_gsum = nullptr;               // its scan's group sums, raw and scanned
     uint32_t* seg_gsum2 = nullptr;
     uint64_t seg_bsum_cap = 0, seg_list_cap = 0, seg_large_cap = 0, seg_tstart_cap = 0, seg_table_cap = 0, seg_gsum_cap = 0, seg_gsum2_cap = 0;
-    // rsx_segmented_topk (capi_topk.inc): the segmented sort's scratch above, plus (grown the same way)
+    // rsx_segmented_topk (capi_topk.inc) and rsx_segmented_select (capi_select.inc, R ranks: R entries where the top-k has one): the
+    // segmented sort's scratch above, plus (grown the same way)
     rsx::TopkState* topk_state = nullptr;       // select state of every large segment
     uint32_t* topk_start = nullptr;             // [large segment][256]: counts of the group tiles a segment begins in
     uint32_t* topk_cont = nullptr;              // [group][256]: counts of the segment a group of tiles continues
@@ -1265,7 +1267,7 @@ int check_scan_timeout(rsx_engine* e, int status)
         const uint32_t v = *bad;
         if (v != 0) {
             *bad = 0;
-            return fail(status, ("rsx_segmented_sort / rsx_segmented_topk: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; it was neither read nor "
+            return fail(status, ("rsx_segmented_sort / rsx_segmented_topk / rsx_segmented_select: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; it was neither read nor "
                                  "written (the first such segment of the call; reported once; the engine remains usable)").c_str());
         }
     }
@@ -2384,6 +2386,7 @@ int rsx_peer_enable(rsx_engine* e, int peer_device)
 #include "capi_msd.inc"
 #include "capi_segmented.inc"
 #include "capi_topk.inc"
+#include "capi_select.inc"
 
 int rsx_key_range(rsx_engine* e, const void* d_keys, uint64_t n, uint64_t* lo, uint64_t* hi)
 {
