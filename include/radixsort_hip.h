@@ -364,6 +364,46 @@ int rsx_segmented_topk(rsx_engine* e, const void* d_keys, uint64_t n, const uint
  *   a stream capture. */
 int rsx_segmented_select(rsx_engine* e, const void* d_keys, uint64_t n, const uint64_t* d_offsets, uint64_t num_segments, const uint32_t* d_ranks,
                          uint32_t ranks_per_segment, void* d_keys_out, uint32_t* d_index_out);
+/* rsx_segmented_unique: the distinct keys of every segment, with their counts, first positions and the inverse map (torch.unique with
+ *   return_inverse / return_counts per segment; with RSX_UNIQUE_CONSECUTIVE torch.unique_consecutive / a run-length encoding).
+ *   Segments are those of rsx_segmented_sort: d_offsets is DEVICE memory, num_segments + 1 uint64, segment s = [off[s], off[s+1]).
+ *   d_offsets == NULL means ONE segment [0, n) (num_segments is then ignored): the sort is then the flat rsx_sort_from chain.
+ *   Per segment, let d_0 < d_1 < ... < d_{m-1} be its distinct keys in the engine's direction and order map (ascending, or descending with
+ *   RSX_OPT_DESCENDING; every key kind).  Two keys are equal iff their BIT PATTERNS are equal, which is equality under the order map: for
+ *   float keys -0.0 and +0.0 are two values and NaNs with equal bits are one (torch.unique merges -0.0 with +0.0 and keeps every NaN
+ *   apart).  With RSX_UNIQUE_CONSECUTIVE (flags bit 0) nothing is sorted: the "distinct keys" are the maximal runs of ADJACENT equal keys of
+ *   the segment in input order.  Equal keys on the two sides of a segment boundary are two runs; empty segments have none.  Written:
+ *     d_run_offsets_out  (required; num_segments + 1 uint64, 2 entries when d_offsets is NULL)  uoff[0] = 0, uoff[s+1] = uoff[s] + m_s; uoff[S] is
+ *                        the total number of runs.  The per-run outputs are packed densely across the segments in this order.
+ *     d_keys_out         (required; room for n keys)  d_keys_out[uoff[s] + u] = d_u of segment s, bit pattern unchanged.
+ *     d_counts_out       (NULL to skip; n uint32)  occurrences of that key in the segment (the length of the run).
+ *     d_first_out        (NULL to skip; n uint32)  position relative to off[s] of the key's FIRST occurrence (the lowest index; consecutive
+ *                        mode: where the run starts).
+ *     d_inverse_out      (NULL to skip; n uint32)  for every i in [off[0], off[S]): d_inverse_out[i] = u such that d_keys_out[uoff[s] + u] has
+ *                        the bits of d_keys[i], s the segment of i.  Positions outside [off[0], off[S]) are not written.
+ *   Entries past uoff[S] of the per-run outputs are not written.  The result is bitwise the same from run to run.
+ *   Positions cost a payload: in sorted mode d_first_out / d_inverse_out need an engine created with has_payload = 1 (its permutation
+ *   ping-pong carries the positions through the sort; the call generates them itself, the caller passes no payload) and are refused with
+ *   RSX_HOST_BUFFERS_FAILED otherwise.  Calls without them work on every engine and carry no payload through the sort even on a payload
+ *   engine.  Consecutive mode sorts nothing and serves every output on every engine.
+ *   n == 0, or num_segments == 0 with non-NULL offsets, returns RSX_OK, launches nothing and writes NOTHING — d_run_offsets_out included
+ *   (the caller knows that every entry would be 0).  Unknown flag bits are refused with RSX_CALCULATION_FAILED.
+ *   Buffers: n <= capacity (RSX_RESIZE_FAILED) and n <= 2^31, at most 2^32 - 2 segments; d_keys 16-byte aligned, the offsets and run offsets
+ *   8-byte aligned, the other outputs need only their element alignment.  Any overlap among inputs, outputs and the engine's own buffers is
+ *   refused with RSX_HOST_BUFFERS_FAILED; afterwards rsx_download / rsx_copy_result behave as after rsx_segmented_sort.
+ *   As rsx_segmented_sort: the call is asynchronous on the engine's stream and reads nothing back, every launch is sized from n and
+ *   num_segments.  The sorted keys (and positions) stay in the engine's own buffers; one pass over them on the global grid of 4096-key tiles
+ *   counts the first keys of runs per tile, the table scan of the sort family turns the counts into run ids, a second pass stores the
+ *   runs and scatters the inverse map, and a pass over the runs takes the counts from the positions of neighbouring run starts.  Scratch
+ *   grows on first use of a larger n or num_segments, never inside a stream capture.
+ *   Bad offsets (off[s+1] < off[s] or off[s+1] > n): the packing of every later segment depends on every earlier one, so the contract is
+ *   looser than rsx_segmented_select's.  The next rsx_sync / rsx_check_status reports RSX_CALCULATION_FAILED once, rsx_last_error naming
+ *   the first such segment, exactly as for rsx_segmented_sort; no access leaves d_keys[0, n), d_offsets[0, S] or the stated sizes of the
+ *   outputs; d_run_offsets_out is non-decreasing with uoff[S] <= n (this implementation writes zeros); the engine stays usable.  The
+ *   contents of that call's other outputs are unspecified. */
+#define RSX_UNIQUE_CONSECUTIVE 1   /* flags bit 0: do not sort; collapse runs of ADJACENT equal keys (run-length encode) */
+int rsx_segmented_unique(rsx_engine* e, const void* d_keys, uint64_t n, const uint64_t* d_offsets, uint64_t num_segments, uint32_t flags,
+                         void* d_keys_out, uint64_t* d_run_offsets_out, uint32_t* d_counts_out, uint32_t* d_first_out, uint32_t* d_inverse_out);
 /* Receive buffers other ranks can write to (the peer-store exchange below): rsx_peer_alloc (hipMalloc + an IPC handle to hand to the other
  * PROCESSES, which map it with rsx_peer_open / rsx_peer_close — peer access over xGMI); ranks that are threads of one process use the
  * pointer itself (after rsx_peer_enable, once per other device). */

@@ -36,6 +36,7 @@ OPT_RADIX_BITS, OPT_SELF_SCAN, OPT_SMALL_TILE_MAX_KEYS, OPT_XCD_PHASE, OPT_SELF_
 OPT_DESCENDING = 21
 # key kinds of rsx_create (RSX_KEY_*): float keys sort in IEEE 754 totalOrder (-NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN)
 KEY_UNSIGNED, KEY_SIGNED, KEY_FLOAT = 0, 1, 2
+UNIQUE_CONSECUTIVE = 1     # RSX_UNIQUE_CONSECUTIVE: flags bit 0 of rsx_segmented_unique
 # rsx_experimental_option (include/radixsort_hip_experiments.h): known to the EXPERIMENTS build only (experiments()); the product library refuses them
 XOPT_DEBUG_RAISE_SCAN_TIMEOUT, XOPT_INLINE_SCAN, XOPT_INLINE_SCAN_MAX_GROUPS, XOPT_REORDER8_KERNEL, XOPT_REORDER8_STAY = 16, 17, 18, 19, 20
 EXPERIMENTS_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tools", "_variants", "libradixsort_hip_experiments.so")
@@ -46,7 +47,7 @@ SYMBOLS = [
     "rsx_create", "rsx_destroy", "rsx_set_stream", "rsx_get_stream", "rsx_set_option", "rsx_get_geometry", "rsx_resize",
     "rsx_upload", "rsx_fill_pad", "rsx_download", "rsx_pin_host", "rsx_unpin_host", "rsx_pipeline_submit", "rsx_pipeline_wait", "rsx_host_device_pointer",
     "rsx_histogram", "rsx_scan", "rsx_paste", "rsx_reorder", "rsx_sort", "rsx_sync", "rsx_check_status",
-    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
+    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
 ]
 
 
@@ -154,6 +155,7 @@ def load_library() -> C.CDLL:
         "rsx_segmented_sort": ([P, P, P, U64, P, U64, P, P], I),
         "rsx_segmented_topk": ([P, P, U64, P, U64, C.c_uint32, P, P], I),
         "rsx_segmented_select": ([P, P, U64, P, U64, P, C.c_uint32, P, P], I),
+        "rsx_segmented_unique": ([P, P, U64, P, U64, C.c_uint32, P, P, P, P, P], I),
         "rsx_msd_count": ([P, P, U64, I, I, P], I),
         "rsx_msd_scatter": ([P, P, P, U64, P, P], I),
         "rsx_msd_plan": ([P, P, C.c_uint32, C.c_uint32, I, I, P], I),
@@ -460,6 +462,18 @@ class Engine:
         self._check(self.lib.rsx_segmented_select(
             self._h, C.c_void_p(d_keys), n, C.c_void_p(d_offsets), num_segments, C.c_void_p(d_ranks), ranks_per_segment,
             C.c_void_p(d_keys_out), C.c_void_p(d_index_out)), "rsx_segmented_select")
+
+    def segmented_unique(self, d_keys: int, n: int, d_offsets: int | None, num_segments: int, d_keys_out: int, d_run_offsets_out: int,
+                         d_counts_out: int | None = None, d_first_out: int | None = None, d_inverse_out: int | None = None,
+                         consecutive: bool = False) -> None:
+        """The distinct keys of every segment [off[s], off[s+1]) (consecutive: its runs of adjacent equal keys, nothing sorted), packed
+        densely to d_keys_out, with run_offsets (num_segments + 1 uint64), and optionally counts, first positions relative to off[s] and the
+        inverse map (n uint32 each).  d_offsets None: ONE segment [0, n).  First positions / the inverse map of a sorted call need a payload
+        engine.  Asynchronous on the engine's stream; bad offsets are reported by the next sync() / check_status()."""
+        self._check(self.lib.rsx_segmented_unique(
+            self._h, C.c_void_p(d_keys), n, C.c_void_p(d_offsets) if d_offsets else None, num_segments, UNIQUE_CONSECUTIVE if consecutive else 0,
+            C.c_void_p(d_keys_out), C.c_void_p(d_run_offsets_out), C.c_void_p(d_counts_out) if d_counts_out else None,
+            C.c_void_p(d_first_out) if d_first_out else None, C.c_void_p(d_inverse_out) if d_inverse_out else None), "rsx_segmented_unique")
 
     # -- exchange step of the sharded sort on the top B <= 8 bits ----------------
     def msd_count(self, d_keys: int, n: int, bits: int, world: int, d_counts: int) -> None:
@@ -908,3 +922,91 @@ def quantile(x, q, dim: int = -1, keepdim: bool = False, interpolation: str = "l
     if x.dim() == 0 and not keepdim:
         out = out.reshape(nq)
     return out[0] if scalar_q else out
+
+
+# -- unique on torch tensors ----------------------------------------------------------------------------------------------------------
+def _unique_call(what: str, keys, offsets, want_inverse: bool, want_counts: bool, want_first: bool, descending: bool, consecutive: bool):
+    """One rsx_segmented_unique call on a 1-D device tensor (offsets None: one segment).  Returns (values, run_offsets, inverse, counts,
+    first) with the per-run tensors trimmed to run_offsets[-1] and None for what was not asked for."""
+    import torch
+    if not keys.is_cuda:
+        raise ValueError(f"{what}: the input must be a device tensor (there is no CPU path)")
+    name = str(keys.dtype).replace("torch.", "")
+    if name not in _KEY_DTYPES:
+        raise TypeError(f"{what}: unsupported key type {keys.dtype}")
+    n = keys.numel()
+    if n > (1 << 31):
+        raise ValueError(f"{what}: at most 2^31 elements (rsx_segmented_unique's bound)")
+    nseg = 1 if offsets is None else max(offsets.numel() - 1, 0)
+    dev = keys.device
+    run_offsets = torch.zeros(nseg + 1, dtype=torch.int64, device=dev)
+    values = torch.empty(n, dtype=keys.dtype, device=dev)
+    # the uint32 outputs as int32 tensors: positions and counts stay below 2^31 (n <= 2^31; a count of exactly 2^31 is masked below)
+    inverse = torch.zeros(n, dtype=torch.int32, device=dev) if want_inverse else None
+    counts = torch.empty(n, dtype=torch.int32, device=dev) if want_counts else None
+    first = torch.empty(n, dtype=torch.int32, device=dev) if want_first else None
+    total = 0
+    if n > 0 and nseg > 0:
+        k_in = _aligned_copy(keys, torch)
+        off = None
+        if offsets is not None:
+            off = offsets if offsets.is_contiguous() and offsets.data_ptr() % 8 == 0 else offsets.clone(memory_format=torch.contiguous_format)
+        device = dev.index if dev.index is not None else torch.cuda.current_device()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        positions = (want_inverse or want_first) and not consecutive         # only these travel through the sort as its payload
+        eng = _segmented_engine(device, stream, name, positions, bool(descending), n)
+        eng.segmented_unique(k_in.data_ptr(), n, off.data_ptr() if off is not None else None, nseg, values.data_ptr(), run_offsets.data_ptr(),
+                             counts.data_ptr() if want_counts else None, first.data_ptr() if want_first else None,
+                             inverse.data_ptr() if want_inverse else None, consecutive=consecutive)
+        total = int(run_offsets[-1].item())         # the one read-back (a host synchronisation): how many runs there are
+        eng.check_status()      # reports bad offsets (the call has finished)
+    widen = lambda t: None if t is None else (t.to(torch.int64) & 0xFFFFFFFF)
+    return values[:total], run_offsets, widen(inverse), widen(None if counts is None else counts[:total]), widen(None if first is None else first[:total])
+
+
+def segmented_unique(keys, offsets, return_inverse: bool = False, return_counts: bool = False, return_first: bool = False, descending: bool = False,
+                     consecutive: bool = False):
+    """The distinct keys of every segment [offsets[s], offsets[s+1]) of the 1-D device tensor `keys` in ONE engine call
+    (rsx_segmented_unique): returns (values, run_offsets, [inverse], [counts], [first]).  values holds the distinct keys of segment s,
+    ascending (descending=True: descending), at [run_offsets[s], run_offsets[s+1]); counts and first (position of the key's first
+    occurrence relative to the segment start) are indexed like values; inverse is shaped like keys, inverse[i] = index of keys[i] among
+    its segment's distinct keys (0 outside [offsets[0], offsets[-1])).  All three are int64.  consecutive=True sorts nothing and collapses
+    runs of adjacent equal keys instead (torch.unique_consecutive per segment).  Keys are distinct iff their bit patterns are: float keys
+    follow IEEE 754 totalOrder, so -0.0 and +0.0 are two values and NaNs with equal bits are one (torch.unique merges the zeros and keeps
+    every NaN apart).  values and the per-run outputs are trimmed to run_offsets[-1], which reads one int64 back: one host synchronisation
+    per call, as torch.unique has.  Bad offsets raise RadixSortError."""
+    import torch
+    if keys.dim() != 1:
+        raise ValueError("segmented_unique: keys must be a 1-D device tensor")
+    if not keys.is_cuda:
+        raise ValueError("segmented_unique: keys must be a 1-D device tensor (there is no CPU path)")
+    if offsets is None or offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.device != keys.device:
+        raise ValueError("segmented_unique: offsets must be a 1-D int64 tensor on the keys' device")
+    v, ro, inv, cnt, fst = _unique_call("segmented_unique", keys, offsets, return_inverse, return_counts, return_first, descending, consecutive)
+    return (v, ro) + ((inv,) if return_inverse else ()) + ((cnt,) if return_counts else ()) + ((fst,) if return_first else ())
+
+
+def _unique_flat(what: str, x, return_inverse: bool, return_counts: bool, dim, consecutive: bool):
+    if dim is not None:
+        raise NotImplementedError(f"{what}: dim other than None (unique slices) is not implemented")
+    flat = x.reshape(-1)
+    v, _, inv, cnt, _ = _unique_call(what, flat, None, return_inverse, return_counts, False, False, consecutive)
+    if not return_inverse and not return_counts:
+        return v
+    return (v,) + ((inv.reshape(x.shape),) if return_inverse else ()) + ((cnt,) if return_counts else ())
+
+
+def unique(x, sorted: bool = True, return_inverse: bool = False, return_counts: bool = False, dim=None):
+    """torch.unique(x, sorted, return_inverse, return_counts) of a device tensor, flattened, in ONE rsx_segmented_unique call (the flat sort
+    chain, then the run detection): values ascending, inverse int64 shaped like x, counts int64.  sorted=False is accepted and sorts.
+    dim other than None raises NotImplementedError.  Equal to torch for integer dtypes and for floats without -0.0 and NaN: here keys are
+    distinct iff their bits are (IEEE 754 totalOrder: -0.0 and +0.0 are two values, equal-bit NaNs are one).  Reads the number of distinct
+    values back: one host synchronisation, as torch.unique has.  Supported dtypes: int32, uint32, int64, uint64, float32, float64."""
+    del sorted
+    return _unique_flat("unique", x, return_inverse, return_counts, dim, False)
+
+
+def unique_consecutive(x, return_inverse: bool = False, return_counts: bool = False, dim=None):
+    """torch.unique_consecutive(x, return_inverse, return_counts) of a device tensor, flattened: runs of adjacent equal elements collapsed,
+    nothing sorted (rsx_segmented_unique with RSX_UNIQUE_CONSECUTIVE).  Semantics, dtypes and the one host synchronisation as unique()."""
+    return _unique_flat("unique_consecutive", x, return_inverse, return_counts, dim, True)

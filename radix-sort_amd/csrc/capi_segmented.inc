@@ -69,7 +69,7 @@ int ensure_segmented(rsx_engine* e, const SegShape& s, uint64_t nseg)
 
 template <typename Key>
 int segmented_enqueue(rsx_engine* e, const Key* kin, const uint32_t* pin, uint64_t n, const uint64_t* off, uint64_t nseg, Key* kout,
-                      uint32_t* pout)
+                      uint32_t* pout, bool carry_payload = true)
 {
     const SegShape s = seg_shape(n, nseg);
     int rc = ensure_segmented(e, s, nseg);
@@ -77,7 +77,7 @@ int segmented_enqueue(rsx_engine* e, const Key* kin, const uint32_t* pin, uint64
     Key a = 0, m = 0;
     order_consts<Key>(e, &a, &m);
     const rsx::KeyCodec<Key> both{a, m, a, m}, enc{a, m, Key{0}, Key{0}}, dec{Key{0}, Key{0}, a, m}, none{};
-    const bool payload = e->has_payload;
+    const bool payload = e->has_payload && carry_payload;      // (rsx_segmented_unique without positions: keys alone, even on a payload engine)
     if (!payload) {
         pin = nullptr;
         pout = nullptr;

@@ -15,6 +15,7 @@
 #include "rsx_segmented.hpp"
 #include "rsx_topk.hpp"
 #include "rsx_select.hpp"
+#include "rsx_unique.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -217,6 +218,10 @@ struct rsx_engine {
     uint32_t* topk_start = nullptr;             // [large segment][256]: counts of the group tiles a segment begins in
     uint32_t* topk_cont = nullptr;              // [group][256]: counts of the segment a group of tiles continues
     uint64_t topk_state_cap = 0, topk_start_cap = 0, topk_cont_cap = 0;
+    // rsx_segmented_unique (capi_unique.inc): the segmented sort's scratch above (its table and group sums hold the flat per-tile head
+    // counts; word 1 of seg_temp is the first bad segment of the call), plus the positions 0, 1, 2, ... that a sort carries as its payload
+    uint32_t* uniq_iota = nullptr;              // filled when it grows: its contents never change
+    uint64_t uniq_iota_cap = 0;
 
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -1255,6 +1260,19 @@ int sort_chain(rsx_engine* e, const void* ext_keys, const uint32_t* ext_perm, ui
     return RSX_OK;
 }
 
+// sort_chain that carries no payload this time, even on a payload engine (rsx_segmented_unique without positions).  Every chain reads
+// e->has_payload while it ENQUEUES — no kernel does — so the flag is lowered for the duration of the enqueue; the launches are those of
+// an engine created without a payload, and those of every other caller stay what they were.
+template <typename Key>
+int sort_chain_keys_only(rsx_engine* e, const void* ext_keys, uint64_t count)
+{
+    const bool saved = e->has_payload;
+    e->has_payload = false;
+    const int rc = sort_chain<Key>(e, ext_keys, nullptr, count);
+    e->has_payload = saved;
+    return rc;
+}
+
 // a fused-scan workgroup whose poll ran out leaves a flag: surfaced at the host's next synchronisation point
 // (the flag is a word of mapped pinned host memory that the kernel stores to at system scope: reading it costs no copy and no
 // synchronisation, so it is also looked at by the asynchronous calls — there it reports a time-out of work that has already
@@ -1641,7 +1659,7 @@ int rsx_destroy(rsx_engine* e)
     for (void* p : {static_cast<void*>(e->seg_hdr), static_cast<void*>(e->seg_temp), static_cast<void*>(e->seg_bsum), static_cast<void*>(e->seg_list),
                     static_cast<void*>(e->seg_large), static_cast<void*>(e->seg_tstart), static_cast<void*>(e->seg_table), static_cast<void*>(e->seg_gsum),
                     static_cast<void*>(e->seg_gsum2), static_cast<void*>(e->topk_state), static_cast<void*>(e->topk_start),
-                    static_cast<void*>(e->topk_cont)}) {
+                    static_cast<void*>(e->topk_cont), static_cast<void*>(e->uniq_iota)}) {
         if (p && hipFree(p) != hipSuccess) status = RSX_CLEANUP_FAILED;
     }
     if (e->seg_status_host && hipHostFree(e->seg_status_host) != hipSuccess) status = RSX_CLEANUP_FAILED;
@@ -2387,6 +2405,7 @@ int rsx_peer_enable(rsx_engine* e, int peer_device)
 #include "capi_segmented.inc"
 #include "capi_topk.inc"
 #include "capi_select.inc"
+#include "capi_unique.inc"
 
 int rsx_key_range(rsx_engine* e, const void* d_keys, uint64_t n, uint64_t* lo, uint64_t* hi)
 {
