@@ -404,6 +404,40 @@ int rsx_segmented_select(rsx_engine* e, const void* d_keys, uint64_t n, const ui
 #define RSX_UNIQUE_CONSECUTIVE 1   /* flags bit 0: do not sort; collapse runs of ADJACENT equal keys (run-length encode) */
 int rsx_segmented_unique(rsx_engine* e, const void* d_keys, uint64_t n, const uint64_t* d_offsets, uint64_t num_segments, uint32_t flags,
                          void* d_keys_out, uint64_t* d_run_offsets_out, uint32_t* d_counts_out, uint32_t* d_first_out, uint32_t* d_inverse_out);
+/* rsx_segmented_reduce_by_key: per segment, the distinct keys and the SUM, MIN or MAX of the values that came with each of them (a sparse
+ *   coalesce, torch.unique + index_add_ / scatter_reduce_ in one call, without the inverse map and without atomics).
+ *   Grouping and layout are rsx_segmented_unique's, bit for bit: the runs are the distinct keys of segment s = [off[s], off[s+1]) in the
+ *   engine's direction and order map, equality is equality of bit patterns, the runs are packed densely across the segments
+ *   (d_keys_out[uoff[s] + u], d_run_offsets_out = uoff, num_segments + 1 uint64), d_counts_out is optional (NULL to skip), d_offsets == NULL
+ *   means ONE segment [0, n) on the flat chain.  flags accepts RSX_UNIQUE_CONSECUTIVE and nothing else: with it nothing is sorted and the
+ *   runs of ADJACENT equal keys in input order are reduced (a run-length reduce).
+ *   d_values is indexed like d_keys: n entries of 4 (RSX_VALUE_INT32, _FLOAT32) or 8 bytes (RSX_VALUE_INT64, _FLOAT64), aligned to their
+ *   size; only positions in [off[0], off[S]) are read.  d_values_out (required; room for n values) gets
+ *   d_values_out[uoff[s] + u] = op over the values of that run's elements:
+ *     RSX_REDUCE_SUM   integers wrap (two's complement).  Floats are added in a FIXED ASSOCIATION that is determined by the input alone —
+ *                      keys, values, offsets and n — through the stable order of the run's elements and their places on the grid of
+ *                      4096-element tiles.  It does not depend on the grid size, the engine's capacity, the stream or on what ran before:
+ *                      two calls on equal input give equal bits.  That is a contract.  No atomic touches a value.
+ *     RSX_REDUCE_MIN / _MAX   floats compare as numbers; the result is NaN if any value of the run is NaN (torch's amin / amax); which of
+ *                      -0.0 and +0.0 wins a tie is unspecified.
+ *   Sorted mode carries the positions of the values through the sort as its payload: it needs an engine created with has_payload = 1 (the
+ *   call generates the positions itself) and is refused with RSX_HOST_BUFFERS_FAILED otherwise.  Consecutive mode works on every engine.
+ *   Everything else as rsx_segmented_unique: asynchronous on the engine's stream, nothing read back, every launch sized from n and
+ *   num_segments; n == 0 (or num_segments == 0 with offsets) writes nothing; n <= capacity and n <= 2^31; d_keys 16-byte aligned; any
+ *   overlap among inputs, outputs and the engine's own buffers is refused; bad offsets are reported once by the next rsx_sync /
+ *   rsx_check_status, the outputs of that call then being unspecified but inside their stated sizes; an unknown op, value kind or flag bit
+ *   is refused with RSX_CALCULATION_FAILED.  Per tile one pass reduces the runs that begin and end inside it and leaves two partials (the
+ *   part before its first run start, the part after its last); a second launch joins the partials of the runs that cross tiles. */
+#define RSX_REDUCE_SUM 0
+#define RSX_REDUCE_MIN 1
+#define RSX_REDUCE_MAX 2
+#define RSX_VALUE_INT32 0
+#define RSX_VALUE_INT64 1
+#define RSX_VALUE_FLOAT32 2
+#define RSX_VALUE_FLOAT64 3
+int rsx_segmented_reduce_by_key(rsx_engine* e, const void* d_keys, const void* d_values, uint64_t n, const uint64_t* d_offsets, uint64_t num_segments,
+                                uint32_t flags, uint32_t op, uint32_t value_kind, void* d_keys_out, uint64_t* d_run_offsets_out, void* d_values_out,
+                                uint32_t* d_counts_out);
 /* Receive buffers other ranks can write to (the peer-store exchange below): rsx_peer_alloc (hipMalloc + an IPC handle to hand to the other
  * PROCESSES, which map it with rsx_peer_open / rsx_peer_close — peer access over xGMI); ranks that are threads of one process use the
  * pointer itself (after rsx_peer_enable, once per other device). */

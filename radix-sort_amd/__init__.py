@@ -36,7 +36,9 @@ OPT_RADIX_BITS, OPT_SELF_SCAN, OPT_SMALL_TILE_MAX_KEYS, OPT_XCD_PHASE, OPT_SELF_
 OPT_DESCENDING = 21
 # key kinds of rsx_create (RSX_KEY_*): float keys sort in IEEE 754 totalOrder (-NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN)
 KEY_UNSIGNED, KEY_SIGNED, KEY_FLOAT = 0, 1, 2
-UNIQUE_CONSECUTIVE = 1     # RSX_UNIQUE_CONSECUTIVE: flags bit 0 of rsx_segmented_unique
+UNIQUE_CONSECUTIVE = 1     # RSX_UNIQUE_CONSECUTIVE: flags bit 0 of rsx_segmented_unique and rsx_segmented_reduce_by_key
+REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2                                   # RSX_REDUCE_*: op of rsx_segmented_reduce_by_key
+VALUE_INT32, VALUE_INT64, VALUE_FLOAT32, VALUE_FLOAT64 = 0, 1, 2, 3           # RSX_VALUE_*: its value kinds
 # rsx_experimental_option (include/radixsort_hip_experiments.h): known to the EXPERIMENTS build only (experiments()); the product library refuses them
 XOPT_DEBUG_RAISE_SCAN_TIMEOUT, XOPT_INLINE_SCAN, XOPT_INLINE_SCAN_MAX_GROUPS, XOPT_REORDER8_KERNEL, XOPT_REORDER8_STAY = 16, 17, 18, 19, 20
 EXPERIMENTS_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tools", "_variants", "libradixsort_hip_experiments.so")
@@ -47,7 +49,7 @@ SYMBOLS = [
     "rsx_create", "rsx_destroy", "rsx_set_stream", "rsx_get_stream", "rsx_set_option", "rsx_get_geometry", "rsx_resize",
     "rsx_upload", "rsx_fill_pad", "rsx_download", "rsx_pin_host", "rsx_unpin_host", "rsx_pipeline_submit", "rsx_pipeline_wait", "rsx_host_device_pointer",
     "rsx_histogram", "rsx_scan", "rsx_paste", "rsx_reorder", "rsx_sort", "rsx_sync", "rsx_check_status",
-    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
+    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
 ]
 
 
@@ -156,6 +158,7 @@ def load_library() -> C.CDLL:
         "rsx_segmented_topk": ([P, P, U64, P, U64, C.c_uint32, P, P], I),
         "rsx_segmented_select": ([P, P, U64, P, U64, P, C.c_uint32, P, P], I),
         "rsx_segmented_unique": ([P, P, U64, P, U64, C.c_uint32, P, P, P, P, P], I),
+        "rsx_segmented_reduce_by_key": ([P, P, P, U64, P, U64, C.c_uint32, C.c_uint32, C.c_uint32, P, P, P, P], I),
         "rsx_msd_count": ([P, P, U64, I, I, P], I),
         "rsx_msd_scatter": ([P, P, P, U64, P, P], I),
         "rsx_msd_plan": ([P, P, C.c_uint32, C.c_uint32, I, I, P], I),
@@ -474,6 +477,20 @@ class Engine:
             self._h, C.c_void_p(d_keys), n, C.c_void_p(d_offsets) if d_offsets else None, num_segments, UNIQUE_CONSECUTIVE if consecutive else 0,
             C.c_void_p(d_keys_out), C.c_void_p(d_run_offsets_out), C.c_void_p(d_counts_out) if d_counts_out else None,
             C.c_void_p(d_first_out) if d_first_out else None, C.c_void_p(d_inverse_out) if d_inverse_out else None), "rsx_segmented_unique")
+
+    def segmented_reduce_by_key(self, d_keys: int, d_values: int, n: int, d_offsets: int | None, num_segments: int, op: int, value_kind: int,
+                                d_keys_out: int, d_run_offsets_out: int, d_values_out: int, d_counts_out: int | None = None,
+                                consecutive: bool = False) -> None:
+        """Per segment [off[s], off[s+1]): the distinct keys (consecutive: the runs of adjacent equal keys, nothing sorted) packed densely to
+        d_keys_out as segmented_unique packs them, with run_offsets, and op (REDUCE_SUM / MIN / MAX) over the values of every run's
+        elements in d_values_out (value_kind: VALUE_INT32 / INT64 / FLOAT32 / FLOAT64; d_values is indexed like d_keys), optionally the
+        counts.  Float sums are added in an order fixed by the input alone: equal input, equal bits.  d_offsets None: ONE segment [0, n).
+        A sorted call needs a payload engine.  Asynchronous on the engine's stream; bad offsets are reported by the next sync() /
+        check_status()."""
+        self._check(self.lib.rsx_segmented_reduce_by_key(
+            self._h, C.c_void_p(d_keys), C.c_void_p(d_values), n, C.c_void_p(d_offsets) if d_offsets else None, num_segments,
+            UNIQUE_CONSECUTIVE if consecutive else 0, op, value_kind, C.c_void_p(d_keys_out), C.c_void_p(d_run_offsets_out),
+            C.c_void_p(d_values_out), C.c_void_p(d_counts_out) if d_counts_out else None), "rsx_segmented_reduce_by_key")
 
     # -- exchange step of the sharded sort on the top B <= 8 bits ----------------
     def msd_count(self, d_keys: int, n: int, bits: int, world: int, d_counts: int) -> None:
@@ -1010,3 +1027,86 @@ def unique_consecutive(x, return_inverse: bool = False, return_counts: bool = Fa
     """torch.unique_consecutive(x, return_inverse, return_counts) of a device tensor, flattened: runs of adjacent equal elements collapsed,
     nothing sorted (rsx_segmented_unique with RSX_UNIQUE_CONSECUTIVE).  Semantics, dtypes and the one host synchronisation as unique()."""
     return _unique_flat("unique_consecutive", x, return_inverse, return_counts, dim, True)
+
+
+# -- reduce by key on torch tensors -----------------------------------------------------------------------------------------------------
+_REDUCE_OPS = {"sum": REDUCE_SUM, "min": REDUCE_MIN, "max": REDUCE_MAX, "mean": REDUCE_SUM}
+_VALUE_KINDS = {"int32": VALUE_INT32, "int64": VALUE_INT64, "float32": VALUE_FLOAT32, "float64": VALUE_FLOAT64}
+
+
+def _reduce_call(what: str, keys, values, offsets, op: str, descending: bool, consecutive: bool):
+    """One rsx_segmented_reduce_by_key call on 1-D device tensors (offsets None: one segment).  Returns (unique_keys, run_offsets, reduced,
+    counts) with the per-run tensors trimmed to run_offsets[-1]; counts are always taken (mean needs them)."""
+    import torch
+    if op not in _REDUCE_OPS:
+        raise ValueError(f"{what}: op must be one of 'sum', 'min', 'max', 'mean', not {op!r}")
+    name = str(keys.dtype).replace("torch.", "")
+    if name not in _KEY_DTYPES:
+        raise TypeError(f"{what}: unsupported key type {keys.dtype}")
+    vname = str(values.dtype).replace("torch.", "")
+    if vname not in _VALUE_KINDS:
+        raise TypeError(f"{what}: unsupported value type {values.dtype} (int32, int64, float32 or float64)")
+    if op == "mean" and not values.dtype.is_floating_point:
+        raise TypeError(f"{what}: the mean of integer values is not defined here (convert them to a float type)")
+    if not keys.is_cuda or not values.is_cuda:
+        raise ValueError(f"{what}: keys and values must be device tensors (there is no CPU path)")
+    if values.shape != keys.shape or values.device != keys.device:
+        raise ValueError(f"{what}: values must be shaped like keys and live on the same device")
+    n = keys.numel()
+    if n > (1 << 31):
+        raise ValueError(f"{what}: at most 2^31 elements (rsx_segmented_reduce_by_key's bound)")
+    nseg = 1 if offsets is None else max(offsets.numel() - 1, 0)
+    dev = keys.device
+    run_offsets = torch.zeros(nseg + 1, dtype=torch.int64, device=dev)
+    ukeys = torch.empty(n, dtype=keys.dtype, device=dev)
+    reduced = torch.empty(n, dtype=values.dtype, device=dev)
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    total = 0
+    if n > 0 and nseg > 0:
+        k_in = _aligned_copy(keys, torch)
+        v_in = values.contiguous()
+        off = None
+        if offsets is not None:
+            off = offsets if offsets.is_contiguous() and offsets.data_ptr() % 8 == 0 else offsets.clone(memory_format=torch.contiguous_format)
+        device = dev.index if dev.index is not None else torch.cuda.current_device()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        eng = _segmented_engine(device, stream, name, not consecutive, bool(descending), n)      # the positions travel as the sort's payload
+        eng.segmented_reduce_by_key(k_in.data_ptr(), v_in.data_ptr(), n, off.data_ptr() if off is not None else None, nseg, _REDUCE_OPS[op],
+                                    _VALUE_KINDS[vname], ukeys.data_ptr(), run_offsets.data_ptr(), reduced.data_ptr(), counts.data_ptr(),
+                                    consecutive=consecutive)
+        total = int(run_offsets[-1].item())         # the one read-back (a host synchronisation): how many runs there are
+        eng.check_status()      # reports bad offsets (the call has finished)
+    cnt = counts[:total].to(torch.int64) & 0xFFFFFFFF
+    red = reduced[:total]
+    if op == "mean":
+        red = red / cnt.to(red.dtype)
+    return ukeys[:total], run_offsets, red, cnt
+
+
+def segmented_reduce_by_key(keys, values, offsets, op: str = "sum", descending: bool = False, consecutive: bool = False, return_counts: bool = False):
+    """Per segment [offsets[s], offsets[s+1]) of the 1-D device tensors `keys` and `values`, in ONE engine call
+    (rsx_segmented_reduce_by_key): returns (unique_keys, run_offsets, reduced[, counts]).  unique_keys and run_offsets are
+    segmented_unique's; reduced[run_offsets[s] + u] is op ('sum', 'min', 'max' or 'mean') over the values whose key is that distinct key of
+    segment s.  Values: int32, int64, float32, float64; integer sums wrap, float min / max return NaN if the run holds one, 'mean' (float
+    values only) is the sum divided by the count.  Float sums are added in an order fixed by the input alone: the same call gives the same
+    bits every time, which index_add_ does not.  consecutive=True sorts nothing and reduces the runs of adjacent equal keys.  Reads the
+    number of runs back: one host synchronisation per call.  Bad offsets raise RadixSortError."""
+    import torch
+    if keys.dim() != 1 or values.dim() != 1:
+        raise ValueError("segmented_reduce_by_key: keys and values must be 1-D device tensors")
+    if offsets is None or offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.device != keys.device:
+        raise ValueError("segmented_reduce_by_key: offsets must be a 1-D int64 tensor on the keys' device")
+    k, ro, red, cnt = _reduce_call("segmented_reduce_by_key", keys, values, offsets, op, descending, consecutive)
+    return (k, ro, red) + ((cnt,) if return_counts else ())
+
+
+def reduce_by_key(keys, values, op: str = "sum", consecutive: bool = False, return_counts: bool = False):
+    """The distinct elements of `keys` (flattened, ascending; consecutive=True: its runs of adjacent equal elements) and op over the
+    elements of `values` (same shape, flattened) that came with each: (unique_keys, reduced[, counts]).  What
+    torch.unique(return_inverse=True) followed by index_add_ / scatter_reduce_ computes, in one rsx_segmented_reduce_by_key call, without
+    the inverse map and with float sums that are bitwise reproducible.  Ops, dtypes and the one host synchronisation as
+    segmented_reduce_by_key."""
+    if tuple(keys.shape) != tuple(values.shape):
+        raise ValueError("reduce_by_key: keys and values must have the same shape")
+    k, _, red, cnt = _reduce_call("reduce_by_key", keys.reshape(-1), values.reshape(-1), None, op, False, consecutive)
+    return (k, red) + ((cnt,) if return_counts else ())

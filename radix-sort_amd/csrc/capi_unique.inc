@@ -15,15 +15,25 @@ void unique_write_launch(rsx_engine* e, uint32_t grid, const Key* keys, const ui
                        e->seg_table, ntiles, chunk, uoff, kout, first, inverse, hp);
 }
 
+// What the grouping steps leave for the steps that write the runs: where the grouped keys (and the positions they came from) are, a buffer
+// of n words for the heads' positions, the first-bad-segment word, and the tile grid.
 template <typename Key>
-int unique_enqueue(rsx_engine* e, const Key* kin, uint64_t n, const uint64_t* off, uint64_t nseg, uint32_t flags, Key* kout, uint64_t* uoff,
-                   uint32_t* counts, uint32_t* first, uint32_t* inverse)
+struct UniqGroups {
+    const Key* skeys;
+    const uint32_t* sperm;
+    uint32_t* hp;
+    uint32_t* bad;
+    uint32_t ntiles, chunk, tgrid;
+    uint64_t cus;
+};
+
+// Steps 1 and 2 of rsx_segmented_unique, shared with rsx_segmented_reduce_by_key (capi_reduce.inc): validate the offsets, group equal keys
+// (carry: with the positions as the sort's payload), count the heads per tile, scan, write the run offsets.
+template <typename Key>
+int unique_groups_enqueue(rsx_engine* e, const Key* kin, uint64_t n, const uint64_t* off, uint64_t nseg, bool consecutive, bool carry, uint64_t* uoff,
+                          UniqGroups<Key>* out)
 {
-    const bool consecutive = (flags & RSX_UNIQUE_CONSECUTIVE) != 0;
-    const bool positions = first || inverse;
-    const bool carry = positions && !consecutive;                   // the sort carries the positions as its payload
     const bool seg_sort = off && !consecutive;
-    if (!off) nseg = 1;
     const uint64_t cus = e->num_cus > 0 ? static_cast<uint64_t>(e->num_cus) : 256u;
 
     // launch bounds from n and the segment count alone: the table has one entry per tile of the global grid and one more (rsx_unique.hpp)
@@ -81,7 +91,6 @@ int unique_enqueue(rsx_engine* e, const Key* kin, uint64_t n, const uint64_t* of
         sperm = carry ? e->result_perm : nullptr;
         hp = static_cast<uint32_t*>(e->keys[e->cur ^ 1]);
     }
-    if (!counts) hp = nullptr;
 
     // 2. heads per tile, their flat exclusive scan, the run offsets
     hipLaunchKernelGGL((rsx::unique_count_kernel<Key>), dim3(tgrid), dim3(rsx::kUniqThreads), 0, e->stream, skeys, n, off, nseg, bad, e->seg_table, ntab,
@@ -92,6 +101,34 @@ int unique_enqueue(rsx_engine* e, const Key* kin, uint64_t n, const uint64_t* of
                        nrow, ngroups);
     hipLaunchKernelGGL(rsx::unique_offsets_kernel, dim3(sgrid), dim3(rsx::kUniqSmallThreads), 0, e->stream, off, nseg, n, bad, e->seg_table, uoff,
                        e->seg_status, consecutive ? 1 : 0);
+
+    out->skeys = skeys;
+    out->sperm = sperm;
+    out->hp = hp;
+    out->bad = bad;
+    out->ntiles = ntiles;
+    out->chunk = chunk;
+    out->tgrid = tgrid;
+    out->cus = cus;
+    return RSX_OK;
+}
+
+template <typename Key>
+int unique_enqueue(rsx_engine* e, const Key* kin, uint64_t n, const uint64_t* off, uint64_t nseg, uint32_t flags, Key* kout, uint64_t* uoff,
+                   uint32_t* counts, uint32_t* first, uint32_t* inverse)
+{
+    const bool consecutive = (flags & RSX_UNIQUE_CONSECUTIVE) != 0;
+    const bool positions = first || inverse;
+    if (!off) nseg = 1;
+    UniqGroups<Key> g;
+    const int rc = unique_groups_enqueue<Key>(e, kin, n, off, nseg, consecutive, positions && !consecutive, uoff, &g);
+    if (rc != RSX_OK) return rc;
+    const Key* skeys = g.skeys;
+    const uint32_t* sperm = g.sperm;
+    uint32_t* bad = g.bad;
+    uint32_t* hp = counts ? g.hp : nullptr;
+    const uint32_t ntiles = g.ntiles, chunk = g.chunk, tgrid = g.tgrid;
+    const uint64_t cus = g.cus;
 
     // 3. the runs: keys, first positions, inverse map; then the counts from the heads' positions
     if (positions && sperm) unique_write_launch<Key, true, true>(e, tgrid, skeys, sperm, n, off, nseg, bad, ntiles, chunk, uoff, kout, first, inverse, hp);

@@ -16,6 +16,7 @@
 #include "rsx_topk.hpp"
 #include "rsx_select.hpp"
 #include "rsx_unique.hpp"
+#include "rsx_reduce.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -222,6 +223,9 @@ struct rsx_engine {
     // counts; word 1 of seg_temp is the first bad segment of the call), plus the positions 0, 1, 2, ... that a sort carries as its payload
     uint32_t* uniq_iota = nullptr;              // filled when it grows: its contents never change
     uint64_t uniq_iota_cap = 0;
+    // rsx_segmented_reduce_by_key (capi_reduce.inc): all of the above, plus three 8-byte slots per tile: lead, tail and the flags
+    uint64_t* red_part = nullptr;
+    uint64_t red_part_cap = 0;
 
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -1659,7 +1663,7 @@ int rsx_destroy(rsx_engine* e)
     for (void* p : {static_cast<void*>(e->seg_hdr), static_cast<void*>(e->seg_temp), static_cast<void*>(e->seg_bsum), static_cast<void*>(e->seg_list),
                     static_cast<void*>(e->seg_large), static_cast<void*>(e->seg_tstart), static_cast<void*>(e->seg_table), static_cast<void*>(e->seg_gsum),
                     static_cast<void*>(e->seg_gsum2), static_cast<void*>(e->topk_state), static_cast<void*>(e->topk_start),
-                    static_cast<void*>(e->topk_cont), static_cast<void*>(e->uniq_iota)}) {
+                    static_cast<void*>(e->topk_cont), static_cast<void*>(e->uniq_iota), static_cast<void*>(e->red_part)}) {
         if (p && hipFree(p) != hipSuccess) status = RSX_CLEANUP_FAILED;
     }
     if (e->seg_status_host && hipHostFree(e->seg_status_host) != hipSuccess) status = RSX_CLEANUP_FAILED;
@@ -2406,6 +2410,7 @@ int rsx_peer_enable(rsx_engine* e, int peer_device)
 #include "capi_topk.inc"
 #include "capi_select.inc"
 #include "capi_unique.inc"
+#include "capi_reduce.inc"
 
 int rsx_key_range(rsx_engine* e, const void* d_keys, uint64_t n, uint64_t* lo, uint64_t* hi)
 {
