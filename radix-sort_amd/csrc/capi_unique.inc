@@ -63,8 +63,10 @@ int unique_groups_enqueue(rsx_engine* e, const Key* kin, uint64_t n, const uint6
         }
     }
     if (rc != RSX_OK) return rc;
+    // (a launch, not hipMemsetAsync(bad, 0xFF, 4): with that memset a captured unique + reduce pair replayed as if its offsets were bad,
+    // every run offset 0, though the same calls were right when run eagerly; DESIGN.md, the chain of the segmented unique)
     uint32_t* bad = e->seg_temp + 1;
-    RSX_TRY(hipMemsetAsync(bad, 0xFF, sizeof(uint32_t), e->stream), RSX_CALCULATION_FAILED);
+    hipLaunchKernelGGL(rsx::unique_reset_kernel, dim3(1), dim3(rsx::kWave), 0, e->stream, bad);
     if (off) {
         hipLaunchKernelGGL(rsx::unique_validate_kernel, dim3(sgrid), dim3(rsx::kUniqSmallThreads), 0, e->stream, off, nseg, n, bad);
     }

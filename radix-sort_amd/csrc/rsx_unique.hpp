@@ -2,6 +2,7 @@
 // the inverse map, from keys that are already grouped (the segmented / flat sort's output, or the raw input in consecutive mode).
 // Included by rsx_capi.hip (host side: capi_unique.inc).
 //
+//   unique_reset_kernel      the first-bad-segment word := none (a kernel, so that a captured call replays it as written)
 //   unique_validate_kernel   per segment: off[s+1] < off[s] or off[s+1] > n -> the first such segment (one word; every later kernel leaves at once)
 //   unique_iota_kernel       0, 1, 2, ...: the positions a sort carries as its payload (written when the buffer grows, never again)
 //   unique_count_kernel      per 4096-key tile of the global grid: heads (first keys of runs) -> flat [tile] table; for every off[s] inside the
@@ -49,6 +50,14 @@ __device__ __forceinline__ uint64_t uniq_lower_bound(const uint64_t* __restrict_
         }
     }
     return lo;
+}
+
+// no bad segment seen yet: the word every later kernel of the call tests first
+__global__ __launch_bounds__(kWave) void unique_reset_kernel(uint32_t* __restrict__ bad)
+{
+    if (threadIdx.x == 0) {
+        *bad = kUniqNoBad;
+    }
 }
 
 __global__ __launch_bounds__(kUniqSmallThreads) void unique_validate_kernel(const uint64_t* __restrict__ off, uint64_t nseg, uint64_t n,

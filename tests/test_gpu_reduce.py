@@ -220,10 +220,9 @@ def test_2p16_distinct_values_at_2p24(rsx):
         check(x, v, None, got, "sum", how=how)
 
 
-def test_runs_against_tile_and_segment_boundaries(rsx):
-    """a run that starts in the last element of a tile, one that ends exactly at a tile boundary, runs crossing several tiles inside a
-    segment that ends mid-tile, equal keys on both sides of a segment boundary"""
-    rng = np.random.default_rng(8)
+def boundary_layout():
+    """(keys, offsets): a run that starts in the last element of a tile, one that ends exactly at a tile boundary, runs crossing several
+    tiles inside a segment that ends mid-tile, equal keys on both sides of a segment boundary"""
     T = 4096
     runs = [T - 1, 1 + T, 3 * T + 100, 5, T - 105, 2 * T, 7, 6 * T + 9, 1, 1, T - 2, 2 * T + 1, 300]
     x = np.repeat(np.arange(len(runs)) * 3 + 11, runs).astype(np.uint32)
@@ -231,6 +230,14 @@ def test_runs_against_tile_and_segment_boundaries(rsx):
     ends = np.cumsum(runs)
     # segment boundaries: inside the 3T+100 run (mid-tile), at a run boundary that is a tile boundary, inside the 6T+9 run twice, and off[S] mid-tile
     off = np.array([0, ends[1] + T + 50, ends[5], ends[6] + 2 * T, ends[6] + 2 * T, ends[6] + 5 * T + 1, n - 123], dtype=np.uint64)
+    return x, off
+
+
+def test_runs_against_tile_and_segment_boundaries(rsx):
+    """the runs of boundary_layout, with and without its offsets, sorted (from shuffled segments) and consecutive"""
+    rng = np.random.default_rng(8)
+    x, off = boundary_layout()
+    n = x.size
     for cons in (False, True):
         for o in (off, None):
             xs = x.copy()

@@ -8,8 +8,9 @@ import subprocess
 import numpy as np
 import pytest
 
-from _reduce_ref import OPS, reduce_oracle, same_values, slow_reduce
-from _unique_ref import FIELDS
+import _unique_ref as U
+from _reduce_ref import OPS, model_sum, reduce_oracle, same_values, slow_reduce
+from _unique_ref import FIELDS, flat_unique, unique_oracle
 from test_gpu_float_keys import random_bits
 from test_gpu_segmented import DTYPES, offsets_from
 from test_segmented import HEADER
@@ -118,6 +119,133 @@ def test_oracle_forms_agree_on_ragged_cases(dtype, descending):
             else:
                 assert int(a["values"][u0:u1].astype(object).sum() - v[lo:hi].astype(object).sum()) % (1 << (8 * np.dtype(vt).itemsize)) == 0
     assert same_values(reduce_oracle(x[:5000], v[:5000])["values"], slow_reduce(x[:5000], v[:5000])["values"])
+
+
+UNIT = {np.dtype(np.float32): 2.0 ** -24, np.dtype(np.float64): 2.0 ** -53}
+EXACT_CAPS = {np.dtype(np.float32): (1024, 1 << 13), np.dtype(np.float64): (1 << 20, 1 << 20)}     # (|v|, run length): tests/test_gpu_reduce.py
+
+
+def model_cases():
+    """(keys, offsets, consecutive) on real 4096-key tiles: runs within float32's exact cap that cross tiles, begin and end on tile
+    edges, segments with off[0] deep in the grid and off[S] before n, one segment, no segment"""
+    rng = np.random.default_rng(41)
+    T = U.TILE
+    n, off, _ = U.deep_layout("mid")
+    yield rng.integers(0, 50, n).astype(np.uint32), off, False
+    runs = rng.choice([1, 2, 17, 300, T - 1, T, T + 1, 6000], size=400)
+    runs = runs[:int(np.searchsorted(np.cumsum(runs), n)) + 1]
+    assert runs.sum() >= n
+    cons = np.repeat(np.arange(runs.size) % 7, runs)[:n].astype(np.uint32)
+    yield cons, off, True
+    n, off, _ = U.deep_layout("edge")
+    yield cons[:n].astype(np.int64), off, True
+    yield rng.integers(0, 9, 3 * T).astype(np.uint32), None, False
+    yield cons[:2 * T + 5], None, True
+    yield rng.integers(0, 30, 5000).astype(np.uint32), np.array([7, 7, 4096, 4096, 4990], dtype=np.uint64), False
+
+
+def test_model_sum_equals_the_oracle_where_every_order_is_exact():
+    """integer-valued inputs within EXACT_CAPS: every association gives the same bits, the written one included"""
+    rng = np.random.default_rng(42)
+    for x, off, cons in model_cases():
+        g = flat_unique(x, off, False, cons)
+        assert all(np.array_equal(g[f], unique_oracle(x, off, False, cons)[f]) for f in FIELDS)
+        for vt in (np.float32, np.float64):
+            vmax, rmax = EXACT_CAPS[np.dtype(vt)]
+            v = rng.integers(-vmax, vmax + 1, x.size).astype(vt)
+            assert int(g["counts"].max()) <= rmax
+            want = reduce_oracle(x, v, off, "sum", False, cons)["values"]
+            assert np.array_equal(reduce_oracle(x, v, off, "sum", False, cons, groups=g)["values"], want)
+            got = model_sum(v, g["order"], g["heads"])
+            assert got.dtype == np.dtype(vt) and np.array_equal(got, want.astype(vt)), (cons, vt)
+
+
+def test_model_sum_within_the_any_order_bound_on_general_inputs():
+    rng = np.random.default_rng(43)
+    for x, off, cons in model_cases():
+        g = flat_unique(x, off, False, cons)
+        for vt in (np.float32, np.float64):
+            v = (rng.standard_normal(x.size) * 10.0 ** rng.integers(-6, 7, x.size)).astype(vt)
+            ref = reduce_oracle(x, v, off, "sum", False, cons, groups=g)
+            got = model_sum(v, g["order"], g["heads"])
+            wide = ref["values"].dtype.type
+            err = np.abs(got.astype(wide) - ref["values"])
+            assert np.all(err <= (ref["counts"].astype(wide) - 1) * wide(UNIT[np.dtype(vt)]) * ref["abs"]), (cons, vt)
+            # and the association matters on such inputs: a plain left-to-right sum of a long run gives other bits somewhere
+            if vt is np.float32 and int(ref["counts"].max()) > 1000:
+                starts = np.concatenate([[0], np.cumsum(ref["counts"].astype(np.int64))])
+                vs = v[g["order"]]
+                plain = np.array([np.add.accumulate(vs[a:b], dtype=vt)[-1] for a, b in zip(starts[:-1], starts[1:])], dtype=vt)
+                assert not np.array_equal(plain, got)
+
+
+def test_model_sum_carry_over_70_tiles():
+    """one run of 70 tiles and a bit that begins mid-tile: the second trip of the carry's lane fold (more than 64 leads) and every level of
+    its tree.  Exact where every order is (integer-valued float64), within the any-order bound on general values."""
+    rng = np.random.default_rng(45)
+    T = U.TILE
+    n = 75 * T + 11
+    x = np.full(n, 2, dtype=np.uint32)
+    x[:2000] = 0
+    x[2000:2000 + 70 * T + 1000] = 1
+    for off in (None, np.array([3, 1000, n - 5], dtype=np.uint64)):
+        g = flat_unique(x, off, False, True)
+        assert int(g["counts"].max()) == 70 * T + 1000 and g["heads"][g["counts"].argmax()] % T == 2000
+        v = rng.integers(-(1 << 20), (1 << 20) + 1, n).astype(np.float64)
+        want = reduce_oracle(x, v, off, "sum", False, True, groups=g)["values"]
+        assert np.array_equal(model_sum(v, g["order"], g["heads"]), want.astype(np.float64))
+        for vt in (np.float32, np.float64):
+            v = (rng.standard_normal(n) * 10.0 ** rng.integers(-2, 3, n)).astype(vt)
+            ref = reduce_oracle(x, v, off, "sum", False, True, groups=g)
+            wide = ref["values"].dtype.type
+            err = np.abs(model_sum(v, g["order"], g["heads"]).astype(wide) - ref["values"])
+            assert np.all(err <= (ref["counts"].astype(wide) - 1) * wide(UNIT[np.dtype(vt)]) * ref["abs"]), vt
+            # one dropped lead (a whole tile of the long run) would show: the bound is far below a tile's sum of magnitudes here
+            lost = np.abs(v[2000 + 64 * T:2000 + 65 * T].astype(wide).sum())
+            assert lost > 0
+
+
+def test_model_sum_hand_built_tile():
+    """one tile, heads at 0, 20 and 1000, written out by hand from the header comment of rsx_reduce.hpp"""
+    rng = np.random.default_rng(44)
+    for vt in (np.float32, np.float64):
+        f = np.dtype(vt).type
+        v = (rng.standard_normal(4096) * 10.0 ** rng.integers(-3, 4, 4096)).astype(vt)
+
+        def fold(a):                                  # left to right
+            r = a[0]
+            for t in a[1:]:
+                r = f(r + t)
+            return r
+
+        thread = [fold(v[16 * t:16 * t + 16]) for t in range(256)]          # a thread without a head: all 16
+
+        def scan(p, l, s, k=5):
+            """lane l of the Hillis-Steele scan after distances 1 .. 2^k over the lane partials p, begun afresh at lane s"""
+            if k < 0:
+                return p[l]
+            d = 1 << k
+            if l - d < s:                             # the lanes l-d+1 .. l reach back to s already: nothing is added
+                return scan(p, l, s, k - 1)
+            return f(scan(p, l - d, s, k - 1) + scan(p, l, s, k - 1))
+
+        # run 0 = [0, 20): thread 0 whole, then the four elements of thread 1 before its head
+        run0 = f(thread[0] + fold(v[16:20]))
+        # run 1 = [20, 1000): thread 1 from its head on, the threads 2 .. 61 (lanes of wave 0, scanned from lane 1), thread 62 before its head
+        p0 = [thread[0], fold(v[20:32])] + thread[2:62]
+        run1 = f(scan(p0, 61, 1) + fold(v[992:1000]))
+        # run 2 = [1000, 4096): it leaves the tile, so it is the tile's tail.  Wave 0 ends with lanes 62 (from its head on) and 63; the
+        # totals of waves 1 and 2 follow left to right; then wave 3's lanes 0 .. 62 scanned, and thread 255 itself last
+        p0 = thread[:62] + [fold(v[1000:1008]), thread[63]]
+        before = f(f(scan(p0, 63, 62) + scan(thread[64:128], 63, 0)) + scan(thread[128:192], 63, 0))
+        run2 = f(f(before + scan(thread[192:256], 62, 0)) + thread[255])
+        got = model_sum(v, np.arange(4096), np.array([0, 20, 1000]))
+        assert got.tolist() == [run0, run1, run2]
+        # two more tiles of the same run: their leads joined by the carry's tree (lane 0 + lane 1), the tail on the left
+        w = np.concatenate([v, v[::-1], v[5:] * f(3)])
+        lead1, lead2 = model_sum(w[4096:8192], np.arange(4096), np.array([0]))[0], model_sum(np.concatenate([w[8192:], np.zeros(5, vt)]), np.arange(4096), np.array([0]))[0]
+        got = model_sum(w, np.arange(w.size), np.array([0, 20, 1000]))
+        assert got.tolist()[:2] == [run0, run1] and got[2] == f(run2 + f(lead1 + lead2))
 
 
 def test_no_cpu_path(rsx):

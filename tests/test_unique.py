@@ -8,7 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from _unique_ref import same, slow_unique, unique_oracle
+import _unique_ref as U
+from _unique_ref import flat_unique, same, slow_unique, unique_oracle
 from test_gpu_float_keys import random_bits, special
 from test_gpu_segmented import DTYPES, offsets_from
 from test_segmented import HEADER
@@ -110,6 +111,81 @@ def test_oracle_forms_agree_on_ragged_cases(dtype, descending):
                 assert np.array_equal(a["keys"][u0:u1][a["inverse"][lo:hi]], xu[lo:hi])
                 assert int(a["counts"][u0:u1].sum()) == hi - lo
         assert same(unique_oracle(x[:5000]), slow_unique(x[:5000]))
+        for cons in (False, True):                     # the one-sort form: the same dict
+            assert same(flat_unique(x, off, descending, cons), unique_oracle(x, off, descending, cons)), (maker, cons)
+        assert same(flat_unique(x[:5000]), slow_unique(x[:5000]))
+
+
+def small_layouts():
+    """scaled-down copies (tiles of 16 or 64 keys, 4 CUs) of every layout of tests/test_gpu_unique_reduce_paths.py: name -> (n, off, keys)"""
+    out = {}
+    for chunk in (2, 3):
+        out[f"ragged{chunk}"] = U.ragged_layout(chunk, tile=64, cus=4, wg=3, long_tiles=5)[:3]
+    for kind in ("ragged", "aligned", "chunk2"):
+        out[f"dense_{kind}"] = U.dense_layout(kind, tile=16, cus=4)
+    for kind in ("mid", "edge", "none", "none_edge"):
+        out[f"deep_{kind}"] = U.deep_layout(kind, tile=64)
+    return out
+
+
+@pytest.mark.parametrize("name", list(small_layouts()))
+def test_flat_unique_equals_both_forms_on_the_new_layouts(name):
+    n, off, keys = small_layouts()[name]
+    assert keys.size == n and int(off[-1]) <= n and (np.diff(off.astype(np.int64)) >= 0).all()
+    for x in (keys, keys.astype(np.int64) - 2):
+        for descending in (False, True):
+            for cons in (False, True):
+                a = flat_unique(x, off, descending, cons)
+                assert same(a, unique_oracle(x, off, descending, cons)), (descending, cons)
+                assert same(a, slow_unique(x, off, descending, cons)), (descending, cons)
+                assert a["order"].size == int(off[-1]) - int(off[0]) and a["heads"].size == int(a["run_offsets"][-1])
+
+
+def test_tile_grid_mirror():
+    """chunk = ceil(npad / (16 * CUs)): 1 up to 4095 * 4096 keys, 2 up to 8191 * 4096, then 3"""
+    T = U.TILE
+    assert U.tile_grid(1) == {"ntiles": 1, "npad": 16, "chunk": 1, "tgrid": 16}
+    assert U.tile_grid(4095 * T)["chunk"] == 1 and U.tile_grid(4095 * T + 1)["chunk"] == 2
+    assert U.tile_grid(8191 * T)["chunk"] == 2 and U.tile_grid(8191 * T + 1)["chunk"] == 3
+    assert U.tile_grid(1 << 24) == {"ntiles": 4096, "npad": 4112, "chunk": 2, "tgrid": 2056}
+
+
+def test_layouts_reach_their_paths():
+    """Each layout of tests/test_gpu_unique_reduce_paths.py still reaches what it is there for on 256 CUs; if the formulas of
+    unique_groups_enqueue change, this fails first."""
+    T = U.TILE
+    for chunk in (2, 3):
+        n, off, keys, (start, length) = U.ragged_layout(chunk)
+        o = off.astype(np.int64)
+        lens = np.diff(o)
+        assert U.tile_grid(n)["chunk"] == chunk and keys.size == n and o[-1] <= n and (lens >= 0).all()
+        assert (lens == 0).any() and (lens > 3 * T).any() and ((lens > 0) & (lens < 4)).any()
+        assert (o % T == 0).any() and (o % T == 1).any() and (o % T == T - 1).any() and o[0] % T != 0 and o[-1] % T != 0
+        # the long run: longer than 65 tiles, begins mid-tile in the last tile of a workgroup's range, ends in another workgroup's,
+        # no segment border inside it, other keys on both sides
+        assert length > 65 * T and start % T != 0 and (start // T) % chunk == chunk - 1 and (start + length) // T // chunk > start // T // chunk + 20
+        assert (keys[start:start + length] == keys[start]).all() and keys[start - 1] != keys[start] and keys[start + length] != keys[start]
+        s = int(np.searchsorted(o, start, side="right"))
+        assert o[s - 1] < start and o[s] >= start + length and o[s - 1] // T == start // T
+        same_both_sides = keys[o[1:-1] - 1] == keys[o[1:-1]]                  # equal keys on both sides of a segment border
+        assert same_both_sides[lens[:-1] > 0].any()
+    for kind in ("ragged", "aligned", "chunk2"):
+        n, off, keys = U.dense_layout(kind)
+        o = off.astype(np.int64)
+        per = U.offsets_per_tile(o, n)
+        assert n >= 1 << 22 and keys.size == n and per.size == U.tile_grid(n)["ntiles"] + 1
+        assert (per > 256).any() and (per > 512).any() and U.tile_grid(n)["chunk"] == (2 if kind == "chunk2" else 1)
+        lens = np.diff(o)
+        assert lens.max() <= 5 and np.median(lens) <= 3
+        pos, cnt = np.unique(o, return_counts=True)
+        blocks = pos[cnt > 1000]                                              # the three blocks of 1000 empty segments
+        assert blocks.size == 3 and blocks[0] % T not in (0, T - 1) and blocks[1] % T == 0 and blocks[2] == o[-1]
+        assert (o[-1] == n and n % T == 0) if kind == "aligned" else (o[-1] < n and o[-1] % T != 0)
+    for kind in ("mid", "edge", "none", "none_edge"):
+        n, off, keys = U.deep_layout(kind)
+        o = off.astype(np.int64)
+        assert o[0] >= 3 * T and o[-1] <= n - 3 * T and keys.size == n
+        assert (o[0] % T == 0) == (kind in ("edge", "none_edge")) and (o[0] == o[-1]) == kind.startswith("none")
 
 
 def test_no_cpu_path(rsx):
