@@ -438,6 +438,36 @@ int rsx_segmented_unique(rsx_engine* e, const void* d_keys, uint64_t n, const ui
 int rsx_segmented_reduce_by_key(rsx_engine* e, const void* d_keys, const void* d_values, uint64_t n, const uint64_t* d_offsets, uint64_t num_segments,
                                 uint32_t flags, uint32_t op, uint32_t value_kind, void* d_keys_out, uint64_t* d_run_offsets_out, void* d_values_out,
                                 uint32_t* d_counts_out);
+/* rsx_segmented_scan: the running SUM, MIN or MAX of the values inside every segment and, with keys, inside every run of adjacent equal
+ *   keys (a scan by key; torch.cumsum / cummax-without-indices of ragged rows in one call).  Nothing is sorted.
+ *   RESTARTS.  A position i in [off[0], off[S]) is a restart if it starts a non-empty segment, or — d_keys given — if key[i] and key[i-1]
+ *   differ by bit pattern: the head rule of RSX_UNIQUE_CONSECUTIVE, so equal keys on the two sides of a segment boundary are two runs.
+ *   d_offsets == NULL is the one segment [0, n); d_keys == NULL is a pure segmented scan; both NULL is the plain scan.  Keys are read with
+ *   the engine's key width; key kind and direction do not matter.
+ *   RESULTS.  With r(i) the last restart <= i: d_values_out[i] = v[r(i)] o ... o v[i]; with RSX_SCAN_EXCLUSIVE (flags bit 1; bit 0 stays
+ *   RSX_UNIQUE_CONSECUTIVE's and is refused here, as every other bit is) it is v[r(i)] o ... o v[i-1], and the identity at a restart: 0 for
+ *   SUM, the type's largest value (+inf) for MIN, its smallest (-inf) for MAX.  Positions outside [off[0], off[S]) are not written, and
+ *   values there are not read.  Values and ops are rsx_segmented_reduce_by_key's: n entries of RSX_VALUE_INT32, _INT64, _FLOAT32 or
+ *   _FLOAT64; integer sums wrap; for float MIN / MAX a NaN makes every later output of the same run NaN.
+ *   FLOAT SUMS ARE BITWISE REPRODUCIBLE.  d_values_out[i] is a function of values, keys, offsets and n alone, through the element's place
+ *   on the grid of 4096-element tiles and the places of the restarts (the association is written at the top of rsx_scan_by_key.hpp).  It
+ *   does not depend on the grid size, on which workgroup takes a tile, on the engine's capacity, the stream, eager or captured execution,
+ *   or on in-place operation; the exclusive result holds the inclusive result's bits one place further on.  That is a contract.  No
+ *   atomic touches a value and no workgroup waits for another: three launches in stream order (tails per tile, the carries of all tiles,
+ *   the tiles scanned), 2 reads and 1 write of the values, 2 reads of the keys.
+ *   IN PLACE.  d_values_out == d_values exactly is served.  Every other overlap is refused with RSX_HOST_BUFFERS_FAILED: the output with
+ *   the keys or the offsets, a partial overlap with the values, anything with the engine's own buffers.
+ *   THE ENGINE'S SORT STATE IS UNTOUCHED.  The call uses none of the capacity-sized buffers (only per-tile scratch grows, outside stream
+ *   captures), so n may exceed the capacity, and the result of an earlier sort, rsx_copy_result included, stays what it was.  n <= 2^31:
+ *   tile indices and launch sizes are 32-bit words on the grid this family shares, and 2^31 is the bound its other calls are held to.
+ *   Otherwise as the family: asynchronous on the engine's stream, nothing read back, every launch sized from n and num_segments; n == 0
+ *   (or num_segments == 0 with offsets) launches and writes nothing; d_keys 16-byte aligned, values and output aligned to their element
+ *   size, offsets to 8 bytes; an unknown flag bit, op or value kind is refused with RSX_CALCULATION_FAILED.  Offsets are validated on the
+ *   device: with off[s+1] < off[s] or off[s+1] > n the call writes NOTHING and the next rsx_sync / rsx_check_status reports
+ *   RSX_CALCULATION_FAILED once, naming the first such segment; the engine stays usable. */
+#define RSX_SCAN_EXCLUSIVE 2   /* flags bit 1: out[i] folds the elements before i only; a restart holds the identity */
+int rsx_segmented_scan(rsx_engine* e, const void* d_keys, const void* d_values, uint64_t n, const uint64_t* d_offsets, uint64_t num_segments,
+                       uint32_t flags, uint32_t op, uint32_t value_kind, void* d_values_out);
 /* Receive buffers other ranks can write to (the peer-store exchange below): rsx_peer_alloc (hipMalloc + an IPC handle to hand to the other
  * PROCESSES, which map it with rsx_peer_open / rsx_peer_close — peer access over xGMI); ranks that are threads of one process use the
  * pointer itself (after rsx_peer_enable, once per other device). */

@@ -39,6 +39,7 @@ KEY_UNSIGNED, KEY_SIGNED, KEY_FLOAT = 0, 1, 2
 UNIQUE_CONSECUTIVE = 1     # RSX_UNIQUE_CONSECUTIVE: flags bit 0 of rsx_segmented_unique and rsx_segmented_reduce_by_key
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2                                   # RSX_REDUCE_*: op of rsx_segmented_reduce_by_key
 VALUE_INT32, VALUE_INT64, VALUE_FLOAT32, VALUE_FLOAT64 = 0, 1, 2, 3           # RSX_VALUE_*: its value kinds
+SCAN_EXCLUSIVE = 2         # RSX_SCAN_EXCLUSIVE: flags bit 1 of rsx_segmented_scan
 # rsx_experimental_option (include/radixsort_hip_experiments.h): known to the EXPERIMENTS build only (experiments()); the product library refuses them
 XOPT_DEBUG_RAISE_SCAN_TIMEOUT, XOPT_INLINE_SCAN, XOPT_INLINE_SCAN_MAX_GROUPS, XOPT_REORDER8_KERNEL, XOPT_REORDER8_STAY = 16, 17, 18, 19, 20
 EXPERIMENTS_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tools", "_variants", "libradixsort_hip_experiments.so")
@@ -49,7 +50,7 @@ SYMBOLS = [
     "rsx_create", "rsx_destroy", "rsx_set_stream", "rsx_get_stream", "rsx_set_option", "rsx_get_geometry", "rsx_resize",
     "rsx_upload", "rsx_fill_pad", "rsx_download", "rsx_pin_host", "rsx_unpin_host", "rsx_pipeline_submit", "rsx_pipeline_wait", "rsx_host_device_pointer",
     "rsx_histogram", "rsx_scan", "rsx_paste", "rsx_reorder", "rsx_sort", "rsx_sync", "rsx_check_status",
-    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
+    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
 ]
 
 
@@ -159,6 +160,7 @@ def load_library() -> C.CDLL:
         "rsx_segmented_select": ([P, P, U64, P, U64, P, C.c_uint32, P, P], I),
         "rsx_segmented_unique": ([P, P, U64, P, U64, C.c_uint32, P, P, P, P, P], I),
         "rsx_segmented_reduce_by_key": ([P, P, P, U64, P, U64, C.c_uint32, C.c_uint32, C.c_uint32, P, P, P, P], I),
+        "rsx_segmented_scan": ([P, P, P, U64, P, U64, C.c_uint32, C.c_uint32, C.c_uint32, P], I),
         "rsx_msd_count": ([P, P, U64, I, I, P], I),
         "rsx_msd_scatter": ([P, P, P, U64, P, P], I),
         "rsx_msd_plan": ([P, P, C.c_uint32, C.c_uint32, I, I, P], I),
@@ -491,6 +493,18 @@ class Engine:
             self._h, C.c_void_p(d_keys), C.c_void_p(d_values), n, C.c_void_p(d_offsets) if d_offsets else None, num_segments,
             UNIQUE_CONSECUTIVE if consecutive else 0, op, value_kind, C.c_void_p(d_keys_out), C.c_void_p(d_run_offsets_out),
             C.c_void_p(d_values_out), C.c_void_p(d_counts_out) if d_counts_out else None), "rsx_segmented_reduce_by_key")
+
+    def segmented_scan(self, d_keys: int | None, d_values: int, n: int, d_offsets: int | None, num_segments: int, op: int, value_kind: int,
+                       d_values_out: int, exclusive: bool = False) -> None:
+        """The running op (REDUCE_SUM / MIN / MAX) of d_values inside every segment [off[s], off[s+1]) and, with d_keys, inside every run
+        of adjacent equal keys (equal by bits; nothing is sorted) into d_values_out; exclusive: the elements before i only, the identity
+        at a restart.  d_keys None: segments only; d_offsets None: ONE segment [0, n).  d_values_out == d_values scans in place.  Float
+        sums are added in an order fixed by the input alone: equal input, equal bits.  n may exceed the capacity and the engine's sort
+        result is left alone.  Asynchronous on the engine's stream; bad offsets (nothing is written then) are reported by the next
+        sync() / check_status()."""
+        self._check(self.lib.rsx_segmented_scan(
+            self._h, C.c_void_p(d_keys) if d_keys else None, C.c_void_p(d_values), n, C.c_void_p(d_offsets) if d_offsets else None, num_segments,
+            SCAN_EXCLUSIVE if exclusive else 0, op, value_kind, C.c_void_p(d_values_out)), "rsx_segmented_scan")
 
     # -- exchange step of the sharded sort on the top B <= 8 bits ----------------
     def msd_count(self, d_keys: int, n: int, bits: int, world: int, d_counts: int) -> None:
@@ -1110,3 +1124,114 @@ def reduce_by_key(keys, values, op: str = "sum", consecutive: bool = False, retu
         raise ValueError("reduce_by_key: keys and values must have the same shape")
     k, _, red, cnt = _reduce_call("reduce_by_key", keys.reshape(-1), values.reshape(-1), None, op, False, consecutive)
     return (k, red) + ((cnt,) if return_counts else ())
+
+
+# -- scan on torch tensors --------------------------------------------------------------------------------------------------------------
+_SCAN_OPS = {"sum": REDUCE_SUM, "min": REDUCE_MIN, "max": REDUCE_MAX}
+# One small engine per (device, stream, key width): the scan uses none of an engine's capacity-sized buffers, so nobody allocates two sort
+# buffers to take a prefix sum.  The stream is part of the key for the reason given at _SEG_ENGINES (the per-tile scratch serves one call).
+_SCAN_ENGINES: dict = {}
+_SCAN_ENGINE_CAPACITY = 1 << 12
+
+
+def _scan_engine(device: int, stream: int, key_bytes: int) -> "Engine":
+    key = (device, stream, key_bytes)
+    eng = _SCAN_ENGINES.get(key)
+    if eng is None:
+        eng = Engine("uint32" if key_bytes == 4 else "uint64", _SCAN_ENGINE_CAPACITY, payload=False, device=device)
+        eng.set_stream(stream)
+        _SCAN_ENGINES[key] = eng
+    return eng
+
+
+def _scan_call(what: str, keys, values, offsets, op: str, exclusive: bool, out):
+    """One rsx_segmented_scan call on 1-D device tensors (keys None: segments only; offsets None: one segment)."""
+    import torch
+    if op not in _SCAN_OPS:
+        raise ValueError(f"{what}: op must be one of 'sum', 'min', 'max', not {op!r}")
+    vname = str(values.dtype).replace("torch.", "")
+    if vname not in _VALUE_KINDS:
+        raise TypeError(f"{what}: unsupported value type {values.dtype} (int32, int64, float32 or float64)")
+    key_bytes = 4
+    if keys is not None:
+        name = str(keys.dtype).replace("torch.", "")
+        if name not in _KEY_DTYPES:
+            raise TypeError(f"{what}: unsupported key type {keys.dtype}")
+        key_bytes = _KEY_DTYPES[name][0]
+    if not values.is_cuda or (keys is not None and not keys.is_cuda):
+        raise ValueError(f"{what}: keys and values must be device tensors (there is no CPU path)")
+    if values.dim() != 1 or (keys is not None and (keys.shape != values.shape or keys.device != values.device)):
+        raise ValueError(f"{what}: values must be 1-D, and keys shaped like them on the same device")
+    if offsets is not None and (offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.device != values.device):
+        raise ValueError(f"{what}: offsets must be a 1-D int64 tensor on the values' device")
+    if out is not None and (out.dtype != values.dtype or out.shape != values.shape or out.device != values.device or not out.is_contiguous()):
+        raise ValueError(f"{what}: out must be a contiguous tensor like values (out=values scans in place)")
+    n = values.numel()
+    if n > (1 << 31):
+        raise ValueError(f"{what}: at most 2^31 elements (rsx_segmented_scan's bound)")
+    in_place = out is not None and out.data_ptr() == values.data_ptr() and values.is_contiguous()
+    v_in = values if values.is_contiguous() else values.contiguous()          # (aligned to its element size either way)
+    if out is None:
+        out = v_in.clone()                                                      # positions outside [offsets[0], offsets[-1]) keep the input
+    elif not in_place:
+        out.copy_(v_in)
+    nseg = 1 if offsets is None else max(offsets.numel() - 1, 0)
+    if n == 0 or nseg == 0:
+        return out
+    k_in = None if keys is None else _aligned_copy(keys, torch)
+    off = None
+    if offsets is not None:
+        off = offsets if offsets.is_contiguous() and offsets.data_ptr() % 8 == 0 else offsets.clone(memory_format=torch.contiguous_format)
+    dev = values.device
+    device = dev.index if dev.index is not None else torch.cuda.current_device()
+    eng = _scan_engine(device, torch.cuda.current_stream(dev).cuda_stream, key_bytes)
+    eng.segmented_scan(None if k_in is None else k_in.data_ptr(), out.data_ptr() if in_place else v_in.data_ptr(), n,
+                       None if off is None else off.data_ptr(), nseg, _SCAN_OPS[op], _VALUE_KINDS[vname], out.data_ptr(), exclusive=bool(exclusive))
+    eng.check_status()      # reports bad offsets of calls that have already finished; no synchronisation
+    return out
+
+
+def segmented_scan(values, offsets, op: str = "sum", exclusive: bool = False, keys=None, out=None):
+    """The running op ('sum', 'min' or 'max') of the 1-D device tensor `values` inside every segment [offsets[s], offsets[s+1]) in ONE engine
+    call (rsx_segmented_scan).  keys (optional, shaped like values): the scan also restarts wherever two adjacent keys differ by bits.
+    exclusive=True folds the elements before each position only; a segment or run start then holds the identity (0, the largest or the
+    smallest value of the dtype).  Returns a tensor like values; positions outside [offsets[0], offsets[-1]) keep their input value.
+    out=values scans in place, any other out receives the result.  offsets None: one segment.  Values: int32, int64, float32, float64;
+    integer sums wrap; a NaN poisons the rest of its run for float min / max.  Float sums are added in an order fixed by the input alone:
+    the same call gives the same bits every time.  Never synchronises with the host; bad offsets (nothing is written then) raise
+    RadixSortError at a later call or synchronisation of the engine."""
+    return _scan_call("segmented_scan", keys, values, offsets, op, exclusive, out)
+
+
+def scan_by_key(keys, values, op: str = "sum", exclusive: bool = False):
+    """The running op of `values` inside every run of adjacent equal elements of `keys` (same shape, both flattened; equal by bits; nothing
+    is sorted — sort first for a scan grouped by sorted keys): thrust's inclusive / exclusive_scan_by_key.  Returns a tensor shaped like
+    values.  Ops, dtypes and reproducibility as segmented_scan."""
+    if tuple(keys.shape) != tuple(values.shape):
+        raise ValueError("scan_by_key: keys and values must have the same shape")
+    return _scan_call("scan_by_key", keys.reshape(-1), values.reshape(-1), None, op, exclusive, None).reshape(values.shape)
+
+
+def cumsum(x, dim: int = -1):
+    """torch.cumsum(x, dim) on a device tensor: every row along `dim` is one segment of ONE rsx_segmented_scan call.  The result keeps
+    x's dtype: an integer dtype narrower than int64 (int32 here) is NOT promoted to int64 as torch does, its sums wrap.  Float sums are
+    bitwise reproducible (segmented_scan).  Supported dtypes: int32, int64, float32, float64 (TypeError otherwise)."""
+    import torch
+    if str(x.dtype).replace("torch.", "") not in _VALUE_KINDS:
+        raise TypeError(f"cumsum: unsupported dtype {x.dtype} (int32, int64, float32 or float64)")
+    if not x.is_cuda:
+        raise ValueError("cumsum: x must be a device tensor")
+    if x.dim() == 0:
+        return x.clone()
+    dim = dim % x.dim()
+    size = x.shape[dim]
+    xm = x.movedim(dim, -1)
+    if x.numel() == 0:
+        return x.clone()
+    rows = xm.numel() // size
+    flat = xm.contiguous().reshape(-1)
+    if flat.data_ptr() == x.data_ptr():
+        flat = flat.clone()                                                     # the scan runs in place on a tensor of our own
+    offsets = None if rows == 1 else torch.arange(0, rows + 1, device=x.device, dtype=torch.int64) * size
+    res = _scan_call("cumsum", None, flat, offsets, "sum", False, flat)
+    return res.reshape(xm.shape).movedim(-1, dim)

@@ -17,6 +17,7 @@
 #include "rsx_select.hpp"
 #include "rsx_unique.hpp"
 #include "rsx_reduce.hpp"
+#include "rsx_scan_by_key.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -2411,6 +2412,7 @@ int rsx_peer_enable(rsx_engine* e, int peer_device)
 #include "capi_select.inc"
 #include "capi_unique.inc"
 #include "capi_reduce.inc"
+#include "capi_scan.inc"
 
 int rsx_key_range(rsx_engine* e, const void* d_keys, uint64_t n, uint64_t* lo, uint64_t* hi)
 {
