@@ -13,6 +13,10 @@ a restart holds the identity, every other position the inclusive value of the po
 scan_terms      (m, abs): per position the number of elements folded and the sum of their magnitudes in the wide type: what the error
                 bound of a float sum is made of.
 
+layouts         layout_deep (A), layout_long (B), layout_misaligned (C), layout_dense (D), layout_two_tiles (E): (n, offsets, keys) of the
+                paths that tests/test_gpu_scan_paths.py runs, each from a fixed seed; tests/test_scan.py asserts, from the layout alone, that
+                each still reaches the path it is named after.  keys_of_runs and tiny_values are their building blocks.
+
 model_scan      the float sum in the value's OWN type and in the association that rsx_scan_by_key.hpp writes down (ORDER OF A FLOAT SUM):
                 the device's bits, not a bound.  A function of the positions on the 4096-element tile grid, the restarts and the values
                 alone: it takes no grid size and no tiles-per-workgroup.
@@ -223,3 +227,130 @@ def model_scan(values, off=None, keys=None, exclusive=False):
             F = np.where(r, dt.type(0), E)
     out[lo:hi] = F[lo - base:hi - base]
     return out
+
+
+# -- layouts of the paths (tests/test_gpu_scan_paths.py; tests/test_scan.py checks what each reaches) -----------------------------------------
+
+RUNS = [1, 2, 17, 300, 4095, 4096, 4097, 6000]
+CU_COUNTS = (256, 304)                                         # MI355X, MI300X: layout E must give two tiles per workgroup on both
+
+
+def keys_of_runs(n, rng, dtype=np.uint32, choices=RUNS):
+    """adjacent runs of lengths drawn from `choices`; neighbouring runs always differ"""
+    lens = rng.choice(choices, size=n // min(choices) + 1)
+    lens = lens[:int(np.searchsorted(np.cumsum(lens), n)) + 1]
+    return np.repeat(np.arange(lens.size) % 5 + 3, lens)[:n].astype(dtype)
+
+
+def layout_deep(kdtype=None):
+    """A: off[0] in tile 1000 (lane 40 of wave 15 of carry block 0), mid-tile; the first segment is a run of 70 tiles and a bit that crosses
+    the carry-block edge at tile 1024.  With keys: constant but for one change at 1030 * TILE + 5."""
+    start = 1000 * TILE + 2000
+    n = start + 70 * TILE + 1011
+    off = np.array([start, start + 70 * TILE + 1000, n - 5], dtype=np.uint64)
+    keys = None
+    if kdtype is not None:
+        keys = np.full(n, 7, dtype=kdtype)
+        keys[1030 * TILE + 5:] = 8
+    return n, off, keys
+
+
+def layout_long(deep=False):
+    """B: one run of 1100 tiles, longer than a carry block: R enters block 1 as the fold of all 16 waves of block 0.  deep: off[0] in
+    tile 5 (dead lanes 0 .. 4 of block 0, a first tile with elements before off[0]) and off[S] = n - 3."""
+    n = 1100 * TILE + 77
+    return n, (np.array([5 * TILE + 9, n - 3], dtype=np.uint64) if deep else None), None
+
+
+def layout_misaligned():
+    """C: tiles 1 and 2 are whole (the 16-byte paths where the pointer allows), tiles 0 and 3 are not"""
+    n = 3 * TILE + 100
+    return n, np.array([5, 2000, n - 7], dtype=np.uint64), None
+
+
+def _lengths_summing_to(total, rng):
+    """segment lengths drawn from {0, 0, 0, 1, 1, 2, 3} that sum to exactly `total`"""
+    lens = rng.choice([0, 0, 0, 1, 1, 2, 3], size=4 * total + 64)
+    cut = int(np.searchsorted(np.cumsum(lens), total))
+    assert cut < lens.size
+    lens = lens[:cut + 1].copy()
+    lens[-1] -= int(lens.sum()) - total
+    return lens
+
+
+def layout_dense(kind="mixed", kdtype=None):
+    """D: off[0] = TILE + 17 and about one offset per element.  "mixed": lengths from {0, 0, 0, 1, 1, 2, 3}, 5000 consecutive empty
+    segments mid-tile and 5000 whose common offset is exactly 2 * TILE.  "ones": every segment has one element, every element is a restart.
+    "empty" / "empty_edge": nine equal offsets mid-tile / on a tile edge, nothing in range although n > 0.  Keys: runs of 1 .. 3."""
+    rng = np.random.default_rng(504)
+    lo = TILE + 17
+    if kind == "mixed":
+        lens = np.concatenate([_lengths_summing_to(1500, rng), np.zeros(5000, dtype=np.int64), _lengths_summing_to(TILE - 17 - 1500, rng),
+                               np.zeros(5000, dtype=np.int64), _lengths_summing_to(2 * TILE - 300, rng)])
+        off = np.concatenate([[lo], lo + np.cumsum(lens)]).astype(np.uint64)
+        n = 4 * TILE - 289
+    elif kind == "ones":
+        off = np.arange(lo, 3 * TILE + 51, dtype=np.uint64)
+        n = 3 * TILE + 61
+    else:
+        off = np.full(9, lo if kind == "empty" else 2 * TILE, dtype=np.uint64)
+        n = 4 * TILE - 289
+    assert int(off[-1]) <= n
+    return n, off, None if kdtype is None else keys_of_runs(n, rng, kdtype, [1, 2, 3])
+
+
+def layout_two_tiles(cus, offsets=True):
+    """E: the smallest n at which a workgroup walks two tiles (capi_scan.inc: ceil(tiles / (16 * CUs))), u64 keys of RUNS, and segments of
+    up to three tiles from off[0] = 3 to off[S] = n - 7 (or no offsets)"""
+    rng = np.random.default_rng(505)
+    n = two_tiles_n(cus)
+    keys = keys_of_runs(n, rng, np.uint64)
+    off = None
+    if offsets:
+        lens = rng.integers(1, 3 * TILE, size=n // TILE)
+        lens = lens[:int(np.searchsorted(np.cumsum(lens), n - 10))]
+        off = np.concatenate([[3], 3 + np.cumsum(list(lens) + [n - 10 - int(lens.sum())])]).astype(np.uint64)
+    return n, off, keys
+
+
+def two_tiles_n(cus):
+    return TILE * 16 * cus + 1
+
+
+def runs_of(n, off=None, keys=None):
+    """(starts, ends) of every run of the call, in order"""
+    mask, lo, hi = restarts(n, off, keys)
+    heads = np.flatnonzero(mask)
+    return heads, np.concatenate([heads[1:], [hi]]).astype(heads.dtype) if heads.size else heads
+
+
+def nan_sticks(res, lo, pos, end, hi, exclusive=False):
+    """min / max of the run [lo, end) that meets its only NaN at `pos`: every later output of the run is NaN, none before is, and the
+    first output after the run (if the call has one) is not"""
+    first = pos + 1 if exclusive else pos
+    return bool(np.isnan(res[first:end]).all() and not np.isnan(res[lo:first]).any() and (end >= hi or not np.isnan(res[end])))
+
+
+def longest_run(n, off=None, keys=None):
+    mask, lo, hi = restarts(n, off, keys)
+    return int(np.diff(np.concatenate([np.flatnonzero(mask), [hi]])).max()) if hi > lo else 0
+
+
+def tiny_values(vt, n, rng, longest=None):
+    """Floats around the bottom of the normal range.  longest None: general values, subnormal up to a few binades above finfo.tiny, so that
+    partial sums move in and out of the subnormal range and round there.  longest = the longest run of the layout: multiples k * q of the
+    smallest subnormal q, |k| small, and +-tiny alternating every 1000th element; any window holds a net of at most one tiny, so every
+    partial sum of a run is a multiple of q below 2 * tiny, which is representable: every order of the sum is exact, and the sums
+    cross tiny both ways."""
+    vt = np.dtype(vt)
+    fi = np.finfo(vt)
+    if longest is None:
+        return (rng.standard_normal(n) * 2.0 ** rng.integers(-8, 4, n)).astype(vt) * vt.type(fi.tiny)
+    q = float(fi.smallest_subnormal)
+    per_tiny = int(round(float(fi.tiny) / q))                  # 2^23 / 2^52
+    kmax = min(per_tiny // max(longest, 1), 1 << 20)
+    assert kmax >= 1 and per_tiny + longest * kmax <= 2 * per_tiny
+    k = rng.integers(-kmax, kmax + 1, n).astype(np.float64)
+    big = np.arange(0, n, 1000)
+    k[big] = np.where(np.arange(big.size) % 2 == 0, 1.0, -1.0) * per_tiny
+    return (k * q).astype(vt)

@@ -33,25 +33,32 @@ def engine(rsx, keys=None, stream=None, capacity=CAP):
     return eng
 
 
-def run(rsx, v, off=None, keys=None, op="sum", excl=False, eng=None, in_place=False):
+def run(rsx, v, off=None, keys=None, op="sum", excl=False, eng=None, in_place=False, in_shift=0, out_shift=0):
     """One rsx_segmented_scan through the Engine API.  Out of place: the output is pre-filled with the sentinel and followed by a guard
-    band.  In place: the values' own buffer.  Returns (the output's bits, engine)."""
+    band.  In place: the values' own buffer.  in_shift / out_shift: the pointer handed over lies that many ELEMENTS past a 16-byte
+    aligned one (in place: in_shift for both); the bytes before the output must survive like the guard after it.  Returns (the output's
+    bits, engine)."""
     t = _torch()
     n = v.size
     nbytes = n * v.dtype.itemsize
     nseg = 1 if off is None else len(off) - 1
-    v_in = dev(t, np.concatenate([v.view(np.uint8), np.full(GUARD, 0xA5, dtype=np.uint8)]))
+    pre_in = in_shift * v.dtype.itemsize
+    pre_out = pre_in if in_place else out_shift * v.dtype.itemsize
+    v_in = dev(t, np.concatenate([np.full(pre_in, 0x5A, dtype=np.uint8), v.view(np.uint8), np.full(GUARD, 0xA5, dtype=np.uint8)]))
     k_in = None if keys is None else dev(t, keys)
     o = None if off is None else dev(t, np.asarray(off, dtype=np.uint64))
-    out = v_in if in_place else dev(t, np.concatenate([np.full(nbytes, FILL, dtype=np.uint8), np.full(GUARD, 0xA5, dtype=np.uint8)]))
+    out = v_in if in_place else dev(t, np.concatenate([np.full(pre_out, 0x5A, dtype=np.uint8), np.full(nbytes, FILL, dtype=np.uint8),
+                                                       np.full(GUARD, 0xA5, dtype=np.uint8)]))
+    assert v_in.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
     if eng is None:
         eng = engine(rsx, keys)
-    eng.segmented_scan(None if k_in is None else k_in.data_ptr(), v_in.data_ptr(), n, None if o is None else o.data_ptr(), nseg, OPCODE[op],
-                       KIND[v.dtype], out.data_ptr(), exclusive=excl)
+    eng.segmented_scan(None if k_in is None else k_in.data_ptr(), v_in.data_ptr() + pre_in, n, None if o is None else o.data_ptr(), nseg, OPCODE[op],
+                       KIND[v.dtype], out.data_ptr() + pre_out, exclusive=excl)
     t.cuda.synchronize()          # the engine runs on its own stream; a device-wide wait leaves its status word to eng.sync()
     b = out.cpu().numpy().view(np.uint8)
-    assert np.all(b[nbytes:] == 0xA5), "guard band written"
-    return b[:nbytes].copy().view(UINT[v.dtype]), eng
+    assert np.all(b[:pre_out] == 0x5A), "bytes before the output written"
+    assert np.all(b[pre_out + nbytes:] == 0xA5), "guard band written"
+    return b[pre_out:pre_out + nbytes].copy().view(UINT[v.dtype]), eng
 
 
 def sentinel(dt):

@@ -8,21 +8,15 @@ import subprocess
 import numpy as np
 import pytest
 
-from _scan_ref import OPS, TILE, UNIT, WIDE, flat_scan, identity, model_scan, restarts, same_values, scan_oracle, scan_terms
+import _scan_ref as S
+from _scan_ref import BLOCK, OPS, RUNS, TILE, UNIT, WAVE, WIDE, flat_scan, identity, keys_of_runs, model_scan, restarts, same_values, scan_oracle, scan_terms
 from test_gpu_segmented import offsets_from
 from test_segmented import HEADER
 
 VTYPES = (np.int32, np.int64, np.float32, np.float64)
 # the issue's lengths: thread, wave and tile edges, empty segments, a deep start
 LENGTHS = [0, 1, 2, 15, 16, 17, 1023, 1024, 1025, 4095, 4096, 4097, 9000, 0, 3, 20011]
-RUNS = [1, 2, 17, 300, 4095, 4096, 4097, 6000]
-
-
-def keys_of_runs(n, rng, dtype=np.uint32, choices=RUNS):
-    """adjacent runs of lengths drawn from `choices`; neighbouring runs always differ"""
-    lens = rng.choice(choices, size=n // min(choices) + 1)
-    lens = lens[:int(np.searchsorted(np.cumsum(lens), n)) + 1]
-    return np.repeat(np.arange(lens.size) % 5 + 3, lens)[:n].astype(dtype)
+# RUNS and keys_of_runs live in _scan_ref.py, next to the layouts that are built from them
 
 
 def test_symbol_in_header_exports_and_binding(rsx):
@@ -214,6 +208,167 @@ def test_model_scan_hand_built_tile():
         assert np.array_equal(g3[:4095], got[:4095])
         assert g3[8191] == f(tail0 + tail1) and g3[12287] == f(tail0 + f(tail1 + tail2))
         assert g3[4096] == f(tail0 + w[4096]) and g3[8192 + 16] == f(f(g3[8191] + fold(w[8192:8208])) + w[8208])
+
+
+# -- the layouts of tests/test_gpu_scan_paths.py: what each reaches, and the referee on them -----------------------------------------------
+
+PATH_LAYOUTS = {"A": lambda: S.layout_deep(), "A-keys u32": lambda: S.layout_deep(np.uint32), "A-keys u64": lambda: S.layout_deep(np.uint64),
+                "B": lambda: S.layout_long(), "B-deep": lambda: S.layout_long(True), "C": lambda: S.layout_misaligned(),
+                **{f"D {kind}{', keys' if kd else ''}": (lambda kind=kind, kd=kd: S.layout_dense(kind, kd))
+                   for kind in ("mixed", "ones", "empty", "empty_edge") for kd in (None, np.uint32)},
+                "E": lambda: S.layout_two_tiles(256), "E, no offsets": lambda: S.layout_two_tiles(256, False)}      # E as it is on 256 CUs
+
+
+@pytest.mark.parametrize("name", list(PATH_LAYOUTS))
+def test_model_scan_equals_the_oracle_on_the_path_layouts(name):
+    """integer-valued floats with (longest run) * max|v| below 2^24 / 2^53: every partial sum of every order is representable.  (E holds
+    2^24 elements: float32 only.)"""
+    n, off, keys = PATH_LAYOUTS[name]()
+    rng = np.random.default_rng(list(PATH_LAYOUTS).index(name) + 300)
+    longest = S.longest_run(n, off, keys)
+    for vt, cap, most in ((np.float32, 1 << 24, 256), (np.float64, 1 << 53, 1 << 20)):
+        if n > (1 << 23) and vt is np.float64:
+            continue
+        vmax = min(most, (cap - 1) // max(longest, 1))
+        assert vmax >= 1 and longest * vmax < cap                                  # B: a run of about 4.5M elements, |v| <= 3 in float32
+        v = rng.integers(-vmax, vmax + 1, n).astype(vt)
+        lo, hi = (0, n) if off is None else (int(off[0]), int(off[-1]))
+        for excl in (False, True):
+            got = model_scan(v, off, keys, excl)
+            want = scan_oracle(v, off, keys, "sum", excl).astype(vt)
+            assert got.dtype == np.dtype(vt) and np.array_equal(got, want), (name, vt, excl)
+            assert np.array_equal(got[:lo], v[:lo]) and np.array_equal(got[hi:], v[hi:])
+
+
+def test_path_layouts_reach_their_paths():
+    """computed from each layout alone, on the grid of rsx_scan_by_key.hpp: tiles of 4096, waves of 64 tiles, carry blocks of 1024"""
+    tiles_of = lambda a, b: ((b - 1) // TILE - a // TILE + 1)
+    # A: off[0] deep in a wave and in a block, mid-tile; a run with tiles on both sides of tile 1024
+    for kd in (None, np.uint32, np.uint64):
+        n, off, keys = S.layout_deep(kd)
+        a, b = S.runs_of(n, off, keys)
+        t_first = int(off[0]) // TILE
+        assert t_first % WAVE != 0 and t_first % BLOCK != 0 and int(off[0]) % TILE != 0
+        assert np.any((a // TILE) // BLOCK < ((b - 1) // TILE) // BLOCK)
+        assert (a[0], int(b[0])) == (int(off[0]), 1030 * TILE + 5 if kd else int(off[1]))
+        assert keys is None or (keys.dtype == kd and np.flatnonzero(keys[1:] != keys[:-1]).tolist() == [1030 * TILE + 4])
+    # B: a run over all 16 waves of a carry block and at least one wave more; deep: dead lanes before off[0], elements before it in its tile
+    for deep in (False, True):
+        n, off, keys = S.layout_long(deep)
+        a, b = S.runs_of(n, off, keys)
+        assert int(tiles_of(a, b).max()) >= BLOCK + WAVE and keys is None
+        assert not deep or (0 < int(off[0]) // TILE < WAVE and int(off[0]) % TILE != 0 and int(off[-1]) < n)
+    # C: two whole tiles between two partial ones
+    n, off, _ = S.layout_misaligned()
+    lo, hi = int(off[0]), int(off[-1])
+    whole = [t for t in range((n + TILE - 1) // TILE) if t * TILE >= lo and (t + 1) * TILE <= hi]
+    assert len(whole) >= 2 and 0 not in whole and hi // TILE not in whole and lo > 0 and hi < n
+    # D: two groups of more than 4096 equal offsets, one of them on a tile edge, more than 1024 offsets inside one tile
+    n, off, keys = S.layout_dense("mixed", np.uint32)
+    o = off.astype(np.int64)
+    where, count = np.unique(o, return_counts=True)
+    groups = where[count > 4096]
+    assert groups.size >= 2 and np.any(groups % TILE == 0) and np.any(groups % TILE != 0)
+    assert int(np.bincount(o // TILE).max()) > 1024 and int(o[0]) == TILE + 17 and abs(n - 4 * TILE) < 512
+    assert set(np.diff(o).tolist()) == {0, 1, 2, 3} and set(np.diff(np.flatnonzero(np.concatenate([[True], keys[1:] != keys[:-1], [True]]))).tolist()) == {1, 2, 3}
+    n, off, _ = S.layout_dense("ones")
+    mask, lo, hi = restarts(n, off)
+    assert mask[lo:hi].all() and hi - lo > 2 * TILE and lo % TILE != 0
+    for kind, edge in (("empty", False), ("empty_edge", True)):
+        n, off, _ = S.layout_dense(kind)
+        assert n > 0 and off.size == 9 and np.all(off == off[0]) and 0 < int(off[0]) < n and (int(off[0]) % TILE == 0) == edge
+    # E: two tiles per workgroup, and one at the size below
+    for cus in S.CU_COUNTS:
+        n = S.two_tiles_n(cus)
+        tiles = (n + TILE - 1) // TILE
+        assert -(-tiles // (16 * cus)) == 2 and -(-(tiles - 1) // (16 * cus)) == 1
+    n, off, keys = S.layout_two_tiles(256)
+    assert n == S.two_tiles_n(256) and keys.dtype == np.uint64 and keys.size == n and int(off[0]) == 3 and int(off[-1]) == n - 7
+    assert S.layout_two_tiles(256, False)[1] is None
+
+
+def test_referee_forms_agree_on_the_dense_layout():
+    """layout D, where nearly every element is a restart: the loop over the runs and the flat form"""
+    for kind in ("mixed", "ones"):
+        for kd in (None, np.uint32):
+            n, off, keys = S.layout_dense(kind, kd)
+            rng = np.random.default_rng(320)
+            for vt in (np.int32, np.float64):
+                v = rng.integers(-1000, 1001, n).astype(vt)
+                for op in OPS:
+                    w = v.copy()
+                    if op != "sum" and np.dtype(vt).kind == "f":
+                        w[rng.integers(0, 50, n) == 0] = np.nan
+                    for excl in (False, True):
+                        a, b = scan_oracle(w, off, keys, op, excl), flat_scan(w, off, keys, op, excl)
+                        assert a.dtype == b.dtype and same_values(a, b), (kind, kd, vt, op, excl)
+    # every element a restart: the exclusive result is the identity everywhere in range
+    n, off, _ = S.layout_dense("ones")
+    lo, hi = int(off[0]), int(off[-1])
+    v = np.arange(1, n + 1, dtype=np.int32)
+    for op in OPS:
+        assert np.all(scan_oracle(v, off, None, op, True)[lo:hi] == identity(np.int32, op))
+        assert np.array_equal(scan_oracle(v, off, None, op), v)
+    # nothing in range: nothing changes
+    for kind in ("empty", "empty_edge"):
+        n, off, keys = S.layout_dense(kind, np.uint32)
+        v = np.arange(n, dtype=np.float64)
+        assert np.array_equal(scan_oracle(v, off, keys), v) and np.array_equal(model_scan(v, off, keys), v) and np.array_equal(flat_scan(v, off, keys), v)
+
+
+def test_a_nan_sticks_to_the_end_of_its_run_across_tiles():
+    """what tests/test_gpu_scan_paths.py expects of min / max, held by the referee first: a NaN in the second tile of the first run shows
+    in every later output of that run (69 and 1094 tiles; 29 where a key change ends the run) and stops at the next restart"""
+    for n, off, keys in (S.layout_deep(), S.layout_deep(np.uint32), S.layout_long(True)):
+        a, b = S.runs_of(n, off, keys)
+        lo, end, hi = int(a[0]), int(b[0]), int(off[-1])
+        pos = (lo // TILE + 1) * TILE + 77
+        assert (end - pos) // TILE >= 28 and (end < hi or keys is None)
+        for vt in (np.float32, np.float64):
+            v = np.random.default_rng(330).uniform(1.0, 2.0, n).astype(vt)
+            v[pos] = np.nan
+            for op in ("min", "max"):
+                for excl in (False, True):
+                    for form in (scan_oracle, flat_scan) if keys is not None and vt is np.float32 else (scan_oracle,):
+                        assert S.nan_sticks(form(v, off, keys, op, excl), lo, pos, end, hi, excl), (n, vt, op, excl)
+            assert not S.nan_sticks(v, lo, pos, end, hi)                          # (the check can fail)
+
+
+def tiny_layouts():
+    off = offsets_from(LENGTHS, start=3)
+    yield int(off[-1]) + 5, off
+    yield 70 * TILE, None
+
+
+def test_subnormals_and_negative_zero_in_the_referee():
+    """what tests/test_gpu_scan_paths.py expects of sums at the bottom of the float range, held by the referee first: model_scan flushes
+    nothing (where every order is exact it equals the oracle bit for bit, with partial sums on both sides of finfo.tiny), and a run of
+    -0.0 sums to -0.0 at every position in both"""
+    rng = np.random.default_rng(340)
+    for n, off in tiny_layouts():
+        lo, hi = (0, n) if off is None else (int(off[0]), int(off[-1]))
+        for vt in (np.float32, np.float64):
+            bits = {4: np.uint32, 8: np.uint64}[np.dtype(vt).itemsize]
+            tiny = np.finfo(vt).tiny
+            v = S.tiny_values(vt, n, rng, S.longest_run(n, off))
+            assert np.any((v != 0) & (np.abs(v) < tiny)) and np.any(np.abs(v) >= tiny)
+            for excl in (False, True):
+                got, want = model_scan(v, off, None, excl), scan_oracle(v, off, None, "sum", excl)
+                assert np.array_equal(want.astype(vt).astype(want.dtype), want)         # exact: the oracle's sums are values of the type
+                assert np.array_equal(got.view(bits), want.astype(vt).view(bits)), (n, vt, excl)
+            inc = np.abs(got[lo:hi])
+            assert np.any((inc != 0) & (inc < tiny)) and np.any(inc >= tiny) and np.any(np.abs(np.diff(np.sign(inc - tiny))) == 2)
+            g = S.tiny_values(vt, n, rng)                                          # the general ones of the GPU test: both ranges, too
+            assert np.any((g != 0) & (np.abs(g) < tiny)) and np.any(np.abs(g) >= tiny) and not np.any(np.abs(g) > 64 * tiny)
+            s = np.abs(model_scan(g, off)[lo:hi])
+            assert np.any((s != 0) & (s < tiny)) and np.any(s >= tiny)
+            z = g.copy()
+            a, b = (0, n) if off is None else (int(off[12]), int(off[13]))         # the 9000-element segment, or everything
+            assert b - a >= 9000
+            z[a:b] = -0.0
+            minus = np.array([-0.0], dtype=vt).view(bits)[0]
+            assert minus != 0
+            assert np.all(model_scan(z, off)[a:b].view(bits) == minus) and np.all(scan_oracle(z, off).astype(vt)[a:b].view(bits) == minus)
 
 
 def test_no_cpu_path(rsx):
