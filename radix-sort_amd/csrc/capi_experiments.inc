@@ -57,13 +57,14 @@ bool launch_reorder8_experiment(rsx_engine* e, const void* in, void* out, const 
                                 uint32_t chunk_groups, int shift, int byte_pass, bool first_of_chain, int* rc)
 {
     const Key flip = flip_mask<Key>(e);
+    const bool payload = pin && pout;
     *rc = RSX_OK;
     constexpr size_t lds_v2k = rsx::Reorder8V2Layout<Key, kTileThreads, kKeysPerThread, false>::BYTES;
     constexpr size_t lds_v2p = rsx::Reorder8V2Layout<Key, kTileThreads, kKeysPerThread, true>::BYTES;
     constexpr size_t lds_v3k = rsx::Reorder8V3Layout<Key, kTileThreads, kKeysPerThread, false>::BYTES;
     constexpr size_t lds_v3p = rsx::Reorder8V3Layout<Key, kTileThreads, kKeysPerThread, true>::BYTES;
     if (e->reorder8_version == 3 && e->lds_atomics_ordered == 1) {
-        if (e->has_payload) {
+        if (payload) {
             hipLaunchKernelGGL((rsx::reorder8v3_kernel<Key, kTileThreads, kKeysPerThread, true>), dim3(g.blocks), dim3(kTileThreads), lds_v3p, e->stream,
                                static_cast<const Key*>(in), static_cast<Key*>(out), pin, pout, e->table8, e->gsum8, e->cbase8, chunk_groups,
                                count, g.ntiles, g.tiles_per_xcd, g.remap, shift, flip);
@@ -73,7 +74,7 @@ bool launch_reorder8_experiment(rsx_engine* e, const void* in, void* out, const 
                                count, g.ntiles, g.tiles_per_xcd, g.remap, shift, flip);
         }
     } else if (e->reorder8_version == 2) {
-        if (e->has_payload) {
+        if (payload) {
             hipLaunchKernelGGL((rsx::reorder8v2_kernel<Key, kTileThreads, kKeysPerThread, true>), dim3(g.blocks), dim3(kTileThreads), lds_v2p, e->stream,
                                static_cast<const Key*>(in), static_cast<Key*>(out), pin, pout, e->table8, e->gsum8, e->cbase8, chunk_groups,
                                count, g.ntiles, g.tiles_per_xcd, g.remap, shift, flip);
@@ -92,14 +93,14 @@ bool launch_reorder8_experiment(rsx_engine* e, const void* in, void* out, const 
             return true;
         }
         uint32_t* tickets = e->tickets8 + static_cast<size_t>(byte_pass) * rsx::kNumXcd;
-        const bool packed = sizeof(Key) == 4 && e->has_payload && e->r8_packed;
+        const bool packed = sizeof(Key) == 4 && payload && e->r8_packed;
         const dim3 grid(stay_blocks);
         if (packed) {
             const size_t lds = rsx::Reorder8Layout<uint64_t, kTileThreads, kKeysPerThread>::BYTES + r8_extra_lds_for(e, true, false);
             hipLaunchKernelGGL((rsx::reorder8_stay_kernel<uint64_t, kTileThreads, kKeysPerThread, false, true>), grid, dim3(kTileThreads), lds, e->stream,
                                static_cast<const uint64_t*>(in), static_cast<uint64_t*>(out), pin, pout, e->table8, e->gsum8, e->cbase8, chunk_groups,
                                count, g.ntiles, g.tiles_per_xcd, g.remap, shift, static_cast<uint64_t>(flip), tickets);
-        } else if (e->has_payload) {
+        } else if (payload) {
             const size_t lds = rsx::Reorder8Layout<Key, kTileThreads, kKeysPerThread, true>::BYTES + r8_extra_lds_for(e, sizeof(Key) == 8, true);
             hipLaunchKernelGGL((rsx::reorder8_stay_kernel<Key, kTileThreads, kKeysPerThread, true>), grid, dim3(kTileThreads), lds, e->stream,
                                static_cast<const Key*>(in), static_cast<Key*>(out), pin, pout, e->table8, e->gsum8, e->cbase8, chunk_groups,
@@ -166,66 +167,53 @@ int launch_reorder_inline(rsx_engine* e, const void* in, void* out, const uint32
 // chain is passes + 1 dependent launches instead of 2 passes + 1.  Two count buffers alternate between "scanned (and zeroed) by this
 // launch" and "filled by this launch's look-ahead".
 template <typename Key>
-int sort_inline_enqueue(rsx_engine* e, const void* ext_keys, const uint32_t* ext_perm, uint64_t count)
+int sort_inline_enqueue(rsx_engine* e, const SortJob& job)
 {
+    const uint64_t count = job.n;
     const uint32_t ntiles = static_cast<uint32_t>(e->ntiles(count));
     const uint32_t ngroups = (ntiles + rsx::kScanTiles - 1) / rsx::kScanTiles;
-    const void* in = ext_keys ? ext_keys : e->keys[e->cur];
-    const uint32_t* pin = e->has_payload ? (ext_keys ? ext_perm : e->perm[e->cur]) : nullptr;
-    int dst = ext_keys ? e->cur : (e->cur ^ 1);
+    PingPong pp(e, job);
     Bracket whole(e, PH_TOTAL);
     const size_t rows = static_cast<size_t>(ntiles) * RSX_RADIX * 4;
     RSX_TRY(hipMemsetAsync(e->counts_next, 0, rows, e->stream), RSX_CALCULATION_FAILED);      // (a sort that failed midway may have left counts)
     RSX_TRY(hipMemsetAsync(e->counts_next2, 0, rows, e->stream), RSX_CALCULATION_FAILED);
-    int rc = launch_histogram<Key>(e, in, count, e->first_pass * RSX_RADIX_BITS, RSX_RADIX - 1);
+    int rc = launch_histogram<Key>(e, pp.in, count, job.first * RSX_RADIX_BITS, RSX_RADIX - 1);
     if (rc != RSX_OK) return rc;
     uint32_t* bufs[2] = {e->counts_next, e->counts_next2};
     int filled = 1;                      // bufs[filled] holds the counts the NEXT launch scans (none before the first pass); its look-ahead fills the other
-    for (int pass = e->first_pass; pass < e->last_pass; ++pass) {
-        const bool first = pass == e->first_pass, last = pass + 1 == e->last_pass;
-        const bool to_caller = e->final_keys_out && last;
-        void* out = to_caller ? e->final_keys_out : e->keys[dst];
-        uint32_t* pout = e->has_payload ? (to_caller ? e->final_perm_out : e->perm[dst]) : nullptr;
+    for (int pass = job.first; pass < job.last; ++pass) {
+        const bool first = pass == job.first, last = pass + 1 == job.last;
+        pp.target(e, job, last);
         const int shift = pass * RSX_RADIX_BITS;
         if (++e->scan_epoch == 0) e->scan_epoch = 1;
         const rsx::InlineScanArgs iscan{e->gsums, e->globsum2, e->temp, bufs[filled], e->scan_ready, e->scan_timeout, e->scan_epoch, ngroups, first ? 0 : 1};
         uint32_t* next = bufs[filled ^ 1];
-        if (e->has_payload) {
-            rc = last ? launch_reorder_inline<Key, true, false>(e, in, out, pin, pout, count, shift, 0, next, iscan)
-                      : launch_reorder_inline<Key, true, true>(e, in, out, pin, pout, count, shift, shift + RSX_RADIX_BITS, next, iscan);
+        if (job.payload) {
+            rc = last ? launch_reorder_inline<Key, true, false>(e, pp.in, pp.out, pp.pin, pp.pout, count, shift, 0, next, iscan)
+                      : launch_reorder_inline<Key, true, true>(e, pp.in, pp.out, pp.pin, pp.pout, count, shift, shift + RSX_RADIX_BITS, next, iscan);
         } else {
-            rc = last ? launch_reorder_inline<Key, false, false>(e, in, out, nullptr, nullptr, count, shift, 0, next, iscan)
-                      : launch_reorder_inline<Key, false, true>(e, in, out, nullptr, nullptr, count, shift, shift + RSX_RADIX_BITS, next, iscan);
+            rc = last ? launch_reorder_inline<Key, false, false>(e, pp.in, pp.out, nullptr, nullptr, count, shift, 0, next, iscan)
+                      : launch_reorder_inline<Key, false, true>(e, pp.in, pp.out, nullptr, nullptr, count, shift, shift + RSX_RADIX_BITS, next, iscan);
         }
         if (rc != RSX_OK) return rc;
         filled ^= 1;
-        in = out;
-        pin = pout;
-        dst ^= 1;
+        pp.advance();
     }
     e->counted_keys = nullptr;
     e->globsum_live = e->globsum2;
     e->table_valid = true;
     e->globsum_valid = true;
-    if (in == e->keys[0] || in == e->keys[1]) e->cur = (in == e->keys[0]) ? 0 : 1;
-    e->result_external = e->final_keys_out != nullptr;
-    if (e->final_keys_out) {
-        e->result_keys = e->final_keys_out;
-        e->result_perm = e->has_payload ? e->final_perm_out : nullptr;
-    } else {
-        e->result_keys = e->keys[e->cur];
-        e->result_perm = e->has_payload ? e->perm[e->cur] : nullptr;
-    }
+    finish_chain(e, job, pp.in);
     return RSX_OK;
 }
 
 // the inline chain takes a sort when the option is on, the chain is the plain look-ahead one and the table is mid-size
-bool inline_scan_takes(const rsx_engine* e, uint64_t count)
+bool inline_scan_takes(const rsx_engine* e, const SortJob& job)
 {
-    const uint32_t groups = static_cast<uint32_t>((e->ntiles(count) + rsx::kScanTiles - 1) / rsx::kScanTiles);
+    const uint32_t groups = static_cast<uint32_t>((e->ntiles(job.n) + rsx::kScanTiles - 1) / rsx::kScanTiles);
     // (profile mode 1 keeps the separate scan launches: timeScan / timePaste would otherwise be empty; a captured graph would replay a stale epoch)
-    return e->inline_scan && e->lookahead && e->fused_scan && !e->use_graph && e->profile != 1 && count > 0 && e->first_pass < e->last_pass &&
-           e->ntiles(count) > static_cast<uint64_t>(rsx::kSmallScanMaxTiles) && groups <= std::min(e->inline_scan_max_groups, e->inline_scan_limit);
+    return e->inline_scan && e->lookahead && e->fused_scan && !e->use_graph && e->profile != 1 && job.n > 0 && job.first < job.last &&
+           e->ntiles(job.n) > static_cast<uint64_t>(rsx::kSmallScanMaxTiles) && groups <= std::min(e->inline_scan_max_groups, e->inline_scan_limit);
 }
 
 // ---- large buffers as VMM chunks mapped in a chosen order (env RSX_ALLOC_MODE = 1 | 2, RSX_ALLOC_CHUNK_MB) ------------------------

@@ -82,12 +82,10 @@ int unique_groups_enqueue(rsx_engine* e, const Key* kin, uint64_t n, const uint6
         skeys = static_cast<const Key*>(e->keys[1]);
         sperm = carry ? e->perm[1] : nullptr;
     } else if (!consecutive) {
-        const int saved_first = e->first_pass, saved_last = e->last_pass;
-        e->first_pass = 0;
-        e->last_pass = static_cast<int>(e->passes());
-        rc = carry ? sort_chain<Key>(e, kin, e->uniq_iota, n) : sort_chain_keys_only<Key>(e, kin, n);
-        e->first_pass = saved_first;
-        e->last_pass = saved_last;
+        // every pass, whatever the options say; without positions the sort carries no payload, on a payload engine too
+        const int passes = static_cast<int>(e->passes());
+        const SortJob job{kin, carry ? e->uniq_iota : nullptr, n, 0, passes, 0, passes, nullptr, nullptr, carry};
+        rc = sort_chain<Key>(e, job);
         if (rc != RSX_OK) return rc;
         skeys = static_cast<const Key*>(e->result_keys);
         sperm = carry ? e->result_perm : nullptr;

@@ -103,6 +103,7 @@ struct GraphEntry {      // one captured rsx_sort chain
     const uint32_t* pin;
     uint64_t n;
     int cur, first, last, flags;
+    bool payload;
     uint64_t options_epoch;      // rsx_set_option calls seen when the chain was captured: an option may change the launches
     hipStream_t stream;
     hipGraphExec_t exec;
@@ -117,7 +118,6 @@ struct rsx_engine {
     bool is_signed = false;                     // key_kind == RSX_KEY_SIGNED
     int key_kind = RSX_KEY_UNSIGNED;            // RSX_KEY_UNSIGNED / SIGNED / FLOAT
     bool descending = false;                    // RSX_OPT_DESCENDING
-    int codec_first = 0, codec_last = 0;        // pass range of the whole sort under way: its first pass encodes, its last one decodes
     bool has_payload = false;
     uint64_t capacity = 0;
     uint64_t n = 0;
@@ -167,8 +167,6 @@ struct rsx_engine {
     uint64_t splitters[rsx::kMaxSplitters] = {};   // splitters of the current split partition, unsigned sort order
     uint32_t nsplit = 0;
     bool result_external = false;               // the last sort wrote into the caller's buffer (rsx_sort_from_to): nothing to download
-    void* final_keys_out = nullptr;             // rsx_sort_from_to: where the last pass writes
-    uint32_t* final_perm_out = nullptr;
     unsigned long long* range_dev = nullptr;    // per-workgroup {min, max} of rsx_key_range
     unsigned long long* range_host = nullptr;   // pinned mirror
     uint32_t* starts_dev = nullptr;             // 16 bucket starts (rsx_partition)
@@ -283,7 +281,7 @@ struct rsx_engine {
     uint32_t* cnt3[3] = {nullptr, nullptr, nullptr};      // self-scan: three rotating [tile][16] count buffers
     uint64_t small_tile_max_keys = 1u << 19;              // self-scan sorts of at most this many keys use tiles of 256 x 4 keys (env RSX_SMALL_TILE_MAX_KEYS; measured: -20 % up to 2^16, -16 % at 2^18, -6 % at 2^19, +20 % at 2^20)
     int tile_sort = 1;          // rsx_sort: inputs of at most one tile are sorted by ONE workgroup in ONE launch, all passes in LDS (env RSX_TILE_SORT)
-    int first_pass = 0;
+    int first_pass = 0;         // RSX_OPT_FIRST_PASS / RSX_OPT_LAST_PASS: the range rsx_sort and rsx_sort_from run (a SortJob carries it from there)
     int last_pass = 0;
 
     int use_graph = 0;          // RSX_OPT_GRAPH: replay sorts of <= 2^22 keys from a captured hipGraph (measured: no gain, off)
@@ -405,10 +403,6 @@ int pass_codec(const rsx_engine* e, int pass, int width, int first, int last)
     if (!e->codec()) return 0;
     return (pass == first ? kEncode : 0) | (pass + width == last ? kDecode : 0);
 }
-int pass_codec(const rsx_engine* e, int pass, int width)
-{
-    return pass_codec(e, pass, width, e->codec_first, e->codec_last);
-}
 
 int refuse_codec(const char* what)
 {
@@ -432,6 +426,58 @@ Grid grid_for(const rsx_engine* e, uint64_t count, uint32_t tile_keys = kTileKey
     const uint32_t phase = (e->xcd_remap && (rsx::kNumXcd - 1) * want < g.tiles_per_xcd) ? static_cast<uint32_t>(want) : 0u;
     g.remap = (e->xcd_remap ? 1 : 0) | static_cast<int>(phase << 8);
     return g;
+}
+
+// What one sort call runs: filled at the API boundary and handed down the chain by const reference.  A part of a sort (the mixed
+// chain's byte passes, its last nibble) is a copy with fields changed; the engine holds only what outlives a call.
+struct SortJob {
+    const void* keys;               // the caller's input (null: the engine's current buffer) ...
+    const uint32_t* perm;           // ... and its payload
+    uint64_t n;
+    int first, last;                // the passes this job runs, in 4-bit passes
+    int codec_first, codec_last;    // the range of the whole sort: its first pass encodes and its last one decodes the keys of a codec engine
+    void* keys_out;                 // where the last pass writes (null: ping-pong inside the engine)
+    uint32_t* perm_out;
+    bool payload;                   // this call carries one (only ever true on a payload engine)
+
+    int codec(const rsx_engine* e, int pass, int width) const { return pass_codec(e, pass, width, codec_first, codec_last); }
+};
+
+// The ping-pong of one chain.  With external input the first pass reads the caller's buffer (never written) and the chain continues
+// inside the engine's two buffers; the job's last pass writes to the caller's output where there is one.
+struct PingPong {
+    const void* in;
+    const uint32_t* pin;
+    int dst;                        // the engine buffer the next pass writes
+    void* out = nullptr;
+    uint32_t* pout = nullptr;
+
+    PingPong(const rsx_engine* e, const SortJob& job)
+        : in(job.keys ? job.keys : e->keys[e->cur]), pin(!job.payload ? nullptr : job.keys ? job.perm : e->perm[e->cur]), dst(job.keys ? e->cur : (e->cur ^ 1))
+    {
+    }
+    void target(const rsx_engine* e, const SortJob& job, bool last)
+    {
+        const bool to_caller = job.keys_out && last;
+        out = to_caller ? job.keys_out : e->keys[dst];
+        pout = !job.payload ? nullptr : to_caller ? job.perm_out : e->perm[dst];
+    }
+    void advance()
+    {
+        in = out;
+        pin = pout;
+        dst ^= 1;
+    }
+};
+
+// `in` names the buffer holding the result: make it the engine's "inputKeys" where it is one of the engine's
+// (the reference's even pass count guarantees the same, src/RadixSortGPU.cpp:263-266,394-400)
+void finish_chain(rsx_engine* e, const SortJob& job, const void* in)
+{
+    if (in == e->keys[0] || in == e->keys[1]) e->cur = (in == e->keys[0]) ? 0 : 1;
+    e->result_external = job.keys_out != nullptr;
+    e->result_keys = job.keys_out ? job.keys_out : e->keys[e->cur];
+    e->result_perm = !job.payload ? nullptr : job.keys_out ? job.perm_out : e->perm[e->cur];
 }
 
 // the first `nsplit` splitters of the engine narrowed to the key type (0 = not a splitter launch)
@@ -723,7 +769,7 @@ int key_range(rsx_engine* e, const void* d_keys, uint64_t n, uint64_t* lo, uint6
 // exactly as the pass chain would leave them: the result where the chain's last pass would have written it,
 // the order before the last pass in the other ping-pong buffer, table / group sums / total of the last pass.
 template <typename Key, bool PAYLOAD>
-int launch_tile_sort_t(rsx_engine* e, const void* in, void* out, void* before_last, const uint32_t* pin, uint32_t* pout, uint32_t* pbefore_last, uint64_t count)
+int launch_tile_sort_t(rsx_engine* e, const SortJob& job, const void* in, void* out, void* before_last, const uint32_t* pin, uint32_t* pout, uint32_t* pbefore_last)
 {
     using L = rsx::TileSortLayout<Key, kTileThreads, kKeysPerThread>;
     Bracket b(e, PH_REORDER);
@@ -731,50 +777,41 @@ int launch_tile_sort_t(rsx_engine* e, const void* in, void* out, void* before_la
         // (the one-workgroup sort runs the whole range: it encodes on load and decodes on store)
         hipLaunchKernelGGL((rsx::tile_sort_kernel<Key, kTileThreads, kKeysPerThread, PAYLOAD, true>), dim3(1), dim3(kTileThreads), L::BYTES, e->stream,
                            static_cast<const Key*>(in), static_cast<Key*>(out), static_cast<Key*>(before_last), pin, pout, pbefore_last,
-                           static_cast<uint32_t>(count), e->first_pass, e->last_pass, flip_mask<Key>(e), e->table, e->globsum, e->temp,
-                           key_codec<Key>(e, pass_codec(e, e->first_pass, e->last_pass - e->first_pass)));
+                           static_cast<uint32_t>(job.n), job.first, job.last, flip_mask<Key>(e), e->table, e->globsum, e->temp,
+                           key_codec<Key>(e, job.codec(e, job.first, job.last - job.first)));
     } else {
         hipLaunchKernelGGL((rsx::tile_sort_kernel<Key, kTileThreads, kKeysPerThread, PAYLOAD>), dim3(1), dim3(kTileThreads), L::BYTES, e->stream,
                            static_cast<const Key*>(in), static_cast<Key*>(out), static_cast<Key*>(before_last), pin, pout, pbefore_last,
-                           static_cast<uint32_t>(count), e->first_pass, e->last_pass, flip_mask<Key>(e), e->table, e->globsum, e->temp);
+                           static_cast<uint32_t>(job.n), job.first, job.last, flip_mask<Key>(e), e->table, e->globsum, e->temp);
     }
     RSX_TRY(hipGetLastError(), RSX_CALCULATION_FAILED);
     return RSX_OK;
 }
 
 template <typename Key>
-int sort_tile_enqueue(rsx_engine* e, const void* ext_keys, const uint32_t* ext_perm, uint64_t count)
+int sort_tile_enqueue(rsx_engine* e, const SortJob& job)
 {
-    const int npasses = e->last_pass - e->first_pass;
-    const void* in = ext_keys ? ext_keys : e->keys[e->cur];
-    const uint32_t* pin = e->has_payload ? (ext_keys ? ext_perm : e->perm[e->cur]) : nullptr;
-    const int first_dst = ext_keys ? e->cur : (e->cur ^ 1);
-    const int final_buf = first_dst ^ ((npasses - 1) & 1);            // where the chain's last pass writes
-    void* out = e->final_keys_out ? e->final_keys_out : e->keys[final_buf];
-    uint32_t* pout = e->has_payload ? (e->final_keys_out ? e->final_perm_out : e->perm[final_buf]) : nullptr;
-    void* before_last = npasses > 1 ? e->keys[final_buf ^ 1] : nullptr;
-    uint32_t* pbefore_last = (npasses > 1 && e->has_payload) ? e->perm[final_buf ^ 1] : nullptr;
+    const int npasses = job.last - job.first;
+    PingPong pp(e, job);
+    const void* const in = pp.in;
+    pp.dst ^= (npasses - 1) & 1;                                      // where the chain's last pass writes
+    pp.target(e, job, /*last=*/true);
+    void* before_last = npasses > 1 ? e->keys[pp.dst ^ 1] : nullptr;
+    uint32_t* pbefore_last = (npasses > 1 && job.payload) ? e->perm[pp.dst ^ 1] : nullptr;
     // (with internal input and an odd pass count `before_last` is the input buffer itself: the one workgroup has
     // read all of it into registers before anything is written)
     Bracket whole(e, PH_TOTAL);
     e->counted_keys = nullptr;
     e->globsum_live = e->globsum;
-    const int rc = e->has_payload ? launch_tile_sort_t<Key, true>(e, in, out, before_last, pin, pout, pbefore_last, count)
-                                  : launch_tile_sort_t<Key, false>(e, in, out, before_last, nullptr, nullptr, nullptr, count);
+    const int rc = job.payload ? launch_tile_sort_t<Key, true>(e, job, in, pp.out, before_last, pp.pin, pp.pout, pbefore_last)
+                               : launch_tile_sort_t<Key, false>(e, job, in, pp.out, before_last, nullptr, nullptr, nullptr);
     if (rc != RSX_OK) return rc;
     e->last_in = npasses > 1 ? before_last : in;
-    e->last_shift = (e->last_pass - 1) * RSX_RADIX_BITS;
+    e->last_shift = (job.last - 1) * RSX_RADIX_BITS;
     e->table_valid = true;
     e->globsum_valid = true;
-    e->result_external = e->final_keys_out != nullptr;
-    if (e->final_keys_out) {
-        e->result_keys = e->final_keys_out;
-        e->result_perm = e->has_payload ? e->final_perm_out : nullptr;
-    } else {
-        e->cur = final_buf;
-        e->result_keys = e->keys[e->cur];
-        e->result_perm = e->has_payload ? e->perm[e->cur] : nullptr;
-    }
+    pp.advance();
+    finish_chain(e, job, pp.in);
     return RSX_OK;
 }
 
@@ -782,66 +819,53 @@ int sort_tile_enqueue(rsx_engine* e, const void* ext_keys, const uint32_t* ext_p
 // reorder launch per pass; every reorder workgroup derives its own 16 bases from the raw [tile][16] counts (three
 // rotating count buffers, see rsx::SelfScanArgs).  The sort is then `passes + 1` dependent launches instead of `2 passes + 2`.
 template <typename Key, int KPT = kKeysPerThread>
-int sort_selfscan_enqueue(rsx_engine* e, const void* ext_keys, const uint32_t* ext_perm, uint64_t count)
+int sort_selfscan_enqueue(rsx_engine* e, const SortJob& job)
 {
+    const uint64_t count = job.n;
     // KPT < 16: tiles of 256 x KPT keys for small inputs — a tile's trip through the reorder (what every pass of a small sort
     // waits for) is a chain of per-key steps, so a quarter of the keys per thread is a shorter chain; the engine's
     // own [digit][tile] table read-back is not produced in that geometry
     const Grid g = grid_for(e, count, kTileThreads * KPT);
-    const void* in = ext_keys ? ext_keys : e->keys[e->cur];
-    const uint32_t* pin = e->has_payload ? (ext_keys ? ext_perm : e->perm[e->cur]) : nullptr;
-    int dst = ext_keys ? e->cur : (e->cur ^ 1);
+    PingPong pp(e, job);
     Bracket whole(e, PH_TOTAL);
     e->counted_keys = nullptr;
     {
         Bracket b(e, PH_HISTO);
-        if (pass_codec(e, e->first_pass, 1) & kEncode) {
+        if (job.codec(e, job.first, 1) & kEncode) {
             hipLaunchKernelGGL((rsx::histogram_kernel<Key, kTileThreads, KPT, false, true>), dim3(g.blocks), dim3(kTileThreads), 0, e->stream,
-                               static_cast<const Key*>(in), e->table, count, g.ntiles, g.tiles_per_xcd, g.remap, e->first_pass * RSX_RADIX_BITS,
+                               static_cast<const Key*>(pp.in), e->table, count, g.ntiles, g.tiles_per_xcd, g.remap, job.first * RSX_RADIX_BITS,
                                flip_mask<Key>(e), static_cast<uint32_t>(RSX_RADIX - 1), Key{0}, Key{0}, split_set<Key>(e, 0), e->cnt3[0], e->cnt3[1], e->cnt3[2],
                                key_codec<Key>(e, kEncode));
         } else {
             hipLaunchKernelGGL((rsx::histogram_kernel<Key, kTileThreads, KPT, false>), dim3(g.blocks), dim3(kTileThreads), 0, e->stream,
-                               static_cast<const Key*>(in), e->table, count, g.ntiles, g.tiles_per_xcd, g.remap, e->first_pass * RSX_RADIX_BITS,
+                               static_cast<const Key*>(pp.in), e->table, count, g.ntiles, g.tiles_per_xcd, g.remap, job.first * RSX_RADIX_BITS,
                                flip_mask<Key>(e), static_cast<uint32_t>(RSX_RADIX - 1), Key{0}, Key{0}, split_set<Key>(e, 0), e->cnt3[0], e->cnt3[1], e->cnt3[2]);
         }
         RSX_TRY(hipGetLastError(), RSX_CALCULATION_FAILED);
     }
     int i = 0;
-    for (int pass = e->first_pass; pass < e->last_pass; ++pass, ++i) {
-        const bool last = pass + 1 == e->last_pass;
-        const bool to_caller = e->final_keys_out && last;
-        void* out = to_caller ? e->final_keys_out : e->keys[dst];
-        uint32_t* pout = e->has_payload ? (to_caller ? e->final_perm_out : e->perm[dst]) : nullptr;
+    for (int pass = job.first; pass < job.last; ++pass, ++i) {
+        const bool last = pass + 1 == job.last;
+        pp.target(e, job, last);
         const int shift = pass * RSX_RADIX_BITS;
         const rsx::SelfScanArgs self{e->cnt3[i % 3], e->cnt3[(i + 2) % 3], (last && KPT == kKeysPerThread) ? e->table : nullptr};
         uint32_t* next = e->cnt3[(i + 1) % 3];
-        const int cx = pass_codec(e, pass, 1);
+        const int cx = job.codec(e, pass, 1);
         int rc;
-        if (e->has_payload) {
-            rc = last ? launch_reorder_t<Key, true, false, false, KPT>(e, in, out, pin, pout, count, shift, RSX_RADIX - 1, 0, Key{0}, Key{0}, 0, self, next, cx)
-                      : launch_reorder_t<Key, true, true, false, KPT>(e, in, out, pin, pout, count, shift, RSX_RADIX - 1, shift + RSX_RADIX_BITS, Key{0}, Key{0}, 0, self, next, cx);
+        if (job.payload) {
+            rc = last ? launch_reorder_t<Key, true, false, false, KPT>(e, pp.in, pp.out, pp.pin, pp.pout, count, shift, RSX_RADIX - 1, 0, Key{0}, Key{0}, 0, self, next, cx)
+                      : launch_reorder_t<Key, true, true, false, KPT>(e, pp.in, pp.out, pp.pin, pp.pout, count, shift, RSX_RADIX - 1, shift + RSX_RADIX_BITS, Key{0}, Key{0}, 0, self, next, cx);
         } else {
-            rc = last ? launch_reorder_t<Key, false, false, false, KPT>(e, in, out, nullptr, nullptr, count, shift, RSX_RADIX - 1, 0, Key{0}, Key{0}, 0, self, next, cx)
-                      : launch_reorder_t<Key, false, true, false, KPT>(e, in, out, nullptr, nullptr, count, shift, RSX_RADIX - 1, shift + RSX_RADIX_BITS, Key{0}, Key{0}, 0, self, next, cx);
+            rc = last ? launch_reorder_t<Key, false, false, false, KPT>(e, pp.in, pp.out, nullptr, nullptr, count, shift, RSX_RADIX - 1, 0, Key{0}, Key{0}, 0, self, next, cx)
+                      : launch_reorder_t<Key, false, true, false, KPT>(e, pp.in, pp.out, nullptr, nullptr, count, shift, RSX_RADIX - 1, shift + RSX_RADIX_BITS, Key{0}, Key{0}, 0, self, next, cx);
         }
         if (rc != RSX_OK) return rc;
-        in = out;
-        pin = pout;
-        dst ^= 1;
+        pp.advance();
     }
     // (tiles of 1024 keys leave no table in the engine's own geometry; the 4096-key form writes it in its last pass — but no group sums)
     e->table_valid = (KPT == kKeysPerThread);
     e->globsum_valid = false;
-    if (in == e->keys[0] || in == e->keys[1]) e->cur = (in == e->keys[0]) ? 0 : 1;
-    e->result_external = e->final_keys_out != nullptr;
-    if (e->final_keys_out) {
-        e->result_keys = e->final_keys_out;
-        e->result_perm = e->has_payload ? e->final_perm_out : nullptr;
-    } else {
-        e->result_keys = e->keys[e->cur];
-        e->result_perm = e->has_payload ? e->perm[e->cur] : nullptr;
-    }
+    finish_chain(e, job, pp.in);
     return RSX_OK;
 }
 
@@ -951,8 +975,9 @@ int launch_reorder8(rsx_engine* e, const void* in, void* out, const uint32_t* pi
 {
     const Key flip = flip_mask<Key>(e);
     e->last_in = nullptr;            // an 8-bit pass has no counterpart in the reference's geometry: RSX_OPT_REF_DIAGNOSTICS refuses after it (a later 4-bit pass sets it again)
-    const bool packed = sizeof(Key) == 4 && e->has_payload && e->r8_packed;
-    const bool wide = r8_wide_for(e, sizeof(Key) == 8, e->has_payload);
+    const bool payload = pin && pout;
+    const bool packed = sizeof(Key) == 4 && payload && e->r8_packed;
+    const bool wide = r8_wide_for(e, sizeof(Key) == 8, payload);
     const size_t wide_extra = e->r8_extra_lds >= 0 ? static_cast<size_t>(e->r8_extra_lds) : 0;      // (57-62 KiB per workgroup: two per CU as they stand)
     const dim3 grid(g.blocks);
     constexpr size_t lds_packed = rsx::Reorder8Layout<uint64_t, kTileThreads, kKeysPerThread>::BYTES, lds_packed_wide = rsx::Reorder8Layout<uint64_t, 512, 8, false>::BYTES;
@@ -967,7 +992,7 @@ int launch_reorder8(rsx_engine* e, const void* in, void* out, const uint32_t* pi
             launch_reorder8_v<uint64_t, kTileThreads, kKeysPerThread, false, true>(e, grid, lds_packed + r8_extra_lds_for(e, true, false), in, out, pin, pout, count, g,
                                                                                    chunk_groups, shift, static_cast<uint64_t>(flip), cx);
         }
-    } else if (e->has_payload) {
+    } else if (payload) {
         if (wide) {
             launch_reorder8_v<Key, 512, 8, true>(e, grid, lds_pay_wide + wide_extra, in, out, pin, pout, count, g, chunk_groups, shift, flip, cx);
         } else {
@@ -1032,167 +1057,116 @@ int launch_count8(rsx_engine* e, const void* in, uint64_t count, const Grid& g, 
 }
 
 // 8-bit digits: per pass histogram8 -> scan8 (two launches) -> reorder8, half as many passes.  Taken by the sort
-// chain when RSX_OPT_RADIX_BITS is 8 and the pass range [first_pass, last_pass) — counted in 4-bit passes, as
+// chain when RSX_OPT_RADIX_BITS is 8 and the job's pass range [first, last) — counted in 4-bit passes, as
 // everywhere in this API — covers whole bytes.
 template <typename Key>
-int sort8_chain_enqueue(rsx_engine* e, const void* ext_keys, const uint32_t* ext_perm, uint64_t count)
+int sort8_chain_enqueue(rsx_engine* e, const SortJob& job)
 {
+    const uint64_t count = job.n;
     const Grid g = grid_for(e, count);
     const Scan8Shape s = scan8_shape(g.ntiles);
     if (!e->radix8_ready) return fail(RSX_INITIALIZATION_FAILED, "sort8_chain_enqueue: the 8-bit tables were not allocated (ensure_radix8)");
-    const void* in = ext_keys ? ext_keys : e->keys[e->cur];
-    const uint32_t* pin = e->has_payload ? (ext_keys ? ext_perm : e->perm[e->cur]) : nullptr;
-    int dst = ext_keys ? e->cur : (e->cur ^ 1);
+    PingPong pp(e, job);
     Bracket whole(e, PH_TOTAL);
     e->counted_keys = nullptr;
-    for (int pass = e->first_pass; pass < e->last_pass; pass += 2) {
-        const bool to_caller = e->final_keys_out && pass + 2 == e->last_pass;
-        void* out = to_caller ? e->final_keys_out : e->keys[dst];
-        uint32_t* pout = e->has_payload ? (to_caller ? e->final_perm_out : e->perm[dst]) : nullptr;
+    for (int pass = job.first; pass < job.last; pass += 2) {
+        pp.target(e, job, pass + 2 == job.last);
         const int shift = pass * RSX_RADIX_BITS;
-        const int cx = pass_codec(e, pass, 2);      // (the mixed chain's 8-bit part ends before the sort does: it encodes, never decodes)
-        int rc = launch_count8<Key>(e, in, count, g, s, shift, cx);
+        const int cx = job.codec(e, pass, 2);       // (the mixed chain's 8-bit part ends before the sort does: it encodes, never decodes)
+        int rc = launch_count8<Key>(e, pp.in, count, g, s, shift, cx);
         if (rc != RSX_OK) return rc;
         {
             Bracket b(e, PH_REORDER);
 #ifdef RSX_EXPERIMENTS
-            if (e->codec() || !launch_reorder8_experiment<Key>(e, in, out, pin, pout, count, g, s.chunk_groups, shift, pass / 2, pass == e->first_pass, &rc))
+            if (e->codec() || !launch_reorder8_experiment<Key>(e, pp.in, pp.out, pp.pin, pp.pout, count, g, s.chunk_groups, shift, pass / 2, pass == job.first, &rc))
 #endif
-                rc = launch_reorder8<Key>(e, in, out, pin, pout, count, g, s.chunk_groups, shift, cx);
+                rc = launch_reorder8<Key>(e, pp.in, pp.out, pp.pin, pp.pout, count, g, s.chunk_groups, shift, cx);
         }
         if (rc != RSX_OK) return rc;
-        in = out;                                     // (launch_reorder8 cleared last_in: the reference-geometry diagnostics describe 4-bit passes, rsx_download refuses them after this chain)
-        pin = pout;
-        dst ^= 1;
+        pp.advance();                                 // (launch_reorder8 cleared last_in: the reference-geometry diagnostics describe 4-bit passes, rsx_download refuses them after this chain)
     }
     e->table_valid = false;             // the 8-bit tables are [tile][256]: nothing in the engine's [digit][tile] geometry
     e->globsum_valid = false;
-    if (in == e->keys[0] || in == e->keys[1]) e->cur = (in == e->keys[0]) ? 0 : 1;
-    e->result_external = e->final_keys_out != nullptr;
-    if (e->final_keys_out) {
-        e->result_keys = e->final_keys_out;
-        e->result_perm = e->has_payload ? e->final_perm_out : nullptr;
-    } else {
-        e->result_keys = e->keys[e->cur];
-        e->result_perm = e->has_payload ? e->perm[e->cur] : nullptr;
-    }
+    finish_chain(e, job, pp.in);
     return RSX_OK;
 }
 
 #endif
 
 #ifdef RSX_EXPERIMENTS
-template <typename Key> int sort_inline_enqueue(rsx_engine* e, const void* ext_keys, const uint32_t* ext_perm, uint64_t count);
-bool inline_scan_takes(const rsx_engine* e, uint64_t count);
+template <typename Key> int sort_inline_enqueue(rsx_engine* e, const SortJob& job);
+bool inline_scan_takes(const rsx_engine* e, const SortJob& job);
 #endif
 
 template <typename Key>
-int sort_chain_passes(rsx_engine* e, const void* ext_keys, const uint32_t* ext_perm, uint64_t count);
-
-// The sort of passes [first_pass, last_pass): its first pass encodes and its last one decodes the keys of a codec engine,
-// whichever chain (or chains: the mixed one) runs them.
-template <typename Key>
-int sort_chain_enqueue(rsx_engine* e, const void* ext_keys, const uint32_t* ext_perm, uint64_t count)
+int sort_chain_passes(rsx_engine* e, const SortJob& job)
 {
-    e->codec_first = e->first_pass;
-    e->codec_last = e->last_pass;
-    return sort_chain_passes<Key>(e, ext_keys, ext_perm, count);
-}
-
-template <typename Key>
-int sort_chain_passes(rsx_engine* e, const void* ext_keys, const uint32_t* ext_perm, uint64_t count)
-{
+    const uint64_t count = job.n;
     // (8-bit digits pay off from 2^19 keys: below that the 4-bit self-scan chain — 9 launches of a 1024- or 4096-key tile's
     // latency — is faster than 4 passes of four launches; same result either way)
 #if RSX_TILE_THREADS == 256
-    if (e->radix_bits == 8 && count > e->radix8_min_keys && e->first_pass < e->last_pass && (e->first_pass & 1) == 0 && (e->last_pass & 1) == 0) {
-        return sort8_chain_enqueue<Key>(e, ext_keys, ext_perm, count);
+    if (e->radix_bits == 8 && count > e->radix8_min_keys && job.first < job.last && (job.first & 1) == 0 && (job.last & 1) == 0) {
+        return sort8_chain_enqueue<Key>(e, job);
     }
-    if (e->radix_bits == 8 && count > e->radix8_min_keys && (e->first_pass & 1) == 0 && (e->last_pass & 1) == 1 && e->last_pass - e->first_pass >= 3) {
+    if (e->radix_bits == 8 && count > e->radix8_min_keys && (job.first & 1) == 0 && (job.last & 1) == 1 && job.last - job.first >= 3) {
         // an odd range from a byte boundary (the sharded sort's local passes 0 .. P-2): whole bytes with 8-bit digits inside the
         // engine's buffers, then the last nibble as one 4-bit pass into wherever the result was asked for
-        const int first = e->first_pass, last = e->last_pass;
-        void* const keys_out = e->final_keys_out;
-        uint32_t* const perm_out = e->final_perm_out;
-        e->last_pass = last - 1;
-        e->final_keys_out = nullptr;
-        e->final_perm_out = nullptr;
-        int rc = sort8_chain_enqueue<Key>(e, ext_keys, ext_perm, count);
-        e->last_pass = last;
-        e->final_keys_out = keys_out;
-        e->final_perm_out = perm_out;
-        if (rc != RSX_OK) return rc;
-        e->first_pass = last - 1;
-        rc = sort_chain_passes<Key>(e, nullptr, nullptr, count);
-        e->first_pass = first;
-        return rc;
+        SortJob bytes = job, nibble = job;
+        bytes.last = job.last - 1;
+        bytes.keys_out = nullptr;
+        bytes.perm_out = nullptr;
+        nibble.first = job.last - 1;
+        nibble.keys = nullptr;
+        nibble.perm = nullptr;
+        const int rc = sort8_chain_enqueue<Key>(e, bytes);
+        return rc != RSX_OK ? rc : sort_chain_passes<Key>(e, nibble);
     }
 #endif
 #if RSX_PRODUCT_SHAPE
-    if (e->tile_sort && e->profile != 1 && count > 0 && count <= static_cast<uint64_t>(kTileKeys) && e->first_pass < e->last_pass) {
-        return sort_tile_enqueue<Key>(e, ext_keys, ext_perm, count);
+    if (e->tile_sort && e->profile != 1 && count > 0 && count <= static_cast<uint64_t>(kTileKeys) && job.first < job.last) {
+        return sort_tile_enqueue<Key>(e, job);
     }
 #endif
-    if (e->self_scan && e->lookahead && count > static_cast<uint64_t>(kTileKeys) && e->ntiles(count) <= e->self_scan_max && e->first_pass < e->last_pass) {
-        if (count <= e->small_tile_max_keys) return sort_selfscan_enqueue<Key, kSmallKeysPerThread>(e, ext_keys, ext_perm, count);
-        return sort_selfscan_enqueue<Key>(e, ext_keys, ext_perm, count);
+    if (e->self_scan && e->lookahead && count > static_cast<uint64_t>(kTileKeys) && e->ntiles(count) <= e->self_scan_max && job.first < job.last) {
+        if (count <= e->small_tile_max_keys) return sort_selfscan_enqueue<Key, kSmallKeysPerThread>(e, job);
+        return sort_selfscan_enqueue<Key>(e, job);
     }
 #if defined(RSX_EXPERIMENTS) && RSX_PRODUCT_SHAPE
-    if (!e->codec() && inline_scan_takes(e, count)) return sort_inline_enqueue<Key>(e, ext_keys, ext_perm, count);
+    if (!e->codec() && inline_scan_takes(e, job)) return sort_inline_enqueue<Key>(e, job);
 #endif
-    // Ping-pong.  With external input the first pass reads the caller's buffer (never
-    // written) and the chain continues inside the engine's two buffers.
-    const void* in = ext_keys ? ext_keys : e->keys[e->cur];
-    const uint32_t* pin = e->has_payload ? (ext_keys ? ext_perm : e->perm[e->cur]) : nullptr;
-    int dst = ext_keys ? e->cur : (e->cur ^ 1);
+    PingPong pp(e, job);
     Bracket whole(e, PH_TOTAL);
     if (e->lookahead && count > 0) {
         // look-ahead counters start from zero (a previous sort that failed midway may have left some)
         RSX_TRY(hipMemsetAsync(e->counts_next, 0, static_cast<size_t>(e->ntiles(count)) * RSX_RADIX * 4, e->stream), RSX_CALCULATION_FAILED);
     }
-    for (int pass = e->first_pass; pass < e->last_pass; ++pass) {
-        const bool to_caller = e->final_keys_out && pass + 1 == e->last_pass;      // rsx_sort_from_to
-        void* out = to_caller ? e->final_keys_out : e->keys[dst];
-        uint32_t* pout = e->has_payload ? (to_caller ? e->final_perm_out : e->perm[dst]) : nullptr;
+    for (int pass = job.first; pass < job.last; ++pass) {
+        const bool last = pass + 1 == job.last;
+        pp.target(e, job, last);
         const int shift = pass * RSX_RADIX_BITS;
-        const int cx = pass_codec(e, pass, 1);
+        const int cx = job.codec(e, pass, 1);
         int rc;
         if (!e->lookahead) {
-            rc = run_pass<Key>(e, in, out, pin, pout, count, shift, RSX_RADIX - 1, cx);
+            rc = run_pass<Key>(e, pp.in, pp.out, pp.pin, pp.pout, count, shift, RSX_RADIX - 1, cx);
         } else {
             // only the first pass reads the keys for a histogram; every later table was
             // counted by the previous pass's reorder while it scattered (look-ahead)
-            const bool first = pass == e->first_pass;
-            rc = first ? launch_histogram<Key>(e, in, count, shift, RSX_RADIX - 1, Key{0}, Key{0}, 0, cx) : RSX_OK;
+            const bool first = pass == job.first;
+            rc = first ? launch_histogram<Key>(e, pp.in, count, shift, RSX_RADIX - 1, Key{0}, Key{0}, 0, cx) : RSX_OK;
             bool pasted = false;
             if (rc == RSX_OK) pasted = launch_scan_small(e, count, /*from_counts=*/!first, &rc);
             if (rc == RSX_OK && !pasted) pasted = launch_scan_fused(e, count, /*from_counts=*/!first, &rc);
             const bool merged = e->paste_scan != 0;                  // scan #2 inside the paste launch
             if (rc == RSX_OK && !pasted) rc = launch_scan(e, count, /*from_counts=*/!first, /*scan_level2=*/!merged);
             // small tables were scanned and pasted in one launch; otherwise the paste kernel runs
-            const bool last = pass + 1 == e->last_pass;
             if (rc == RSX_OK && !pasted) rc = merged ? launch_paste_scan(e, count) : launch_paste(e, count);
             const int next_shift = last ? -1 : shift + RSX_RADIX_BITS;
-            if (rc == RSX_OK) rc = launch_reorder<Key>(e, in, out, pin, pout, count, shift, RSX_RADIX - 1, next_shift, cx);
+            if (rc == RSX_OK) rc = launch_reorder<Key>(e, pp.in, pp.out, pp.pin, pp.pout, count, shift, RSX_RADIX - 1, next_shift, cx);
         }
         if (rc != RSX_OK) return rc;
-        in = out;
-        pin = pout;
-        dst ^= 1;
+        pp.advance();
     }
-    // `in` now names the buffer holding the result; make it the engine's "inputKeys"
-    // (the reference's even pass count guarantees the same, src/RadixSortGPU.cpp:263-266,394-400)
-    if (in == e->keys[0] || in == e->keys[1]) {
-        e->cur = (in == e->keys[0]) ? 0 : 1;
-    }
-    e->result_external = e->final_keys_out != nullptr;
-    if (e->final_keys_out) {
-        e->result_keys = e->final_keys_out;
-        e->result_perm = e->has_payload ? e->final_perm_out : nullptr;
-    } else {
-        e->result_keys = e->keys[e->cur];
-        e->result_perm = e->has_payload ? e->perm[e->cur] : nullptr;
-    }
+    finish_chain(e, job, pp.in);
     return RSX_OK;
 }
 
@@ -1202,37 +1176,35 @@ int sort_chain_passes(rsx_engine* e, const void* ext_keys, const uint32_t* ext_p
 constexpr uint64_t kGraphMaxKeys = 1ull << 22;
 
 template <typename Key>
-int sort_chain(rsx_engine* e, const void* ext_keys, const uint32_t* ext_perm, uint64_t count)
+int sort_chain(rsx_engine* e, const SortJob& job)
 {
 #if RSX_TILE_THREADS == 256
-    if (e->radix_bits == 8 && count > e->radix8_min_keys) {
+    if (e->radix_bits == 8 && job.n > e->radix8_min_keys) {
         const int rc8 = ensure_radix8<Key>(e);          // before any capture begins
         if (rc8 != RSX_OK) return rc8;
     }
 #endif
     // (the legacy null stream cannot be captured: PyTorch's default stream is that one)
-    const bool graphable = e->use_graph && e->profile == 0 && count > 0 && count <= kGraphMaxKeys && e->stream != nullptr && !e->final_keys_out;
-    if (!graphable) return sort_chain_enqueue<Key>(e, ext_keys, ext_perm, count);
+    const bool graphable = e->use_graph && e->profile == 0 && job.n > 0 && job.n <= kGraphMaxKeys && e->stream != nullptr && !job.keys_out;
+    if (!graphable) return sort_chain_passes<Key>(e, job);
     GraphEntry key{};
-    key.in = ext_keys;
-    key.pin = ext_perm;
-    key.n = count;
+    key.in = job.keys;
+    key.pin = job.perm;
+    key.n = job.n;
     key.cur = e->cur;
-    key.first = e->first_pass;
-    key.last = e->last_pass;
+    key.first = job.first;
+    key.last = job.last;
     key.flags = (e->lookahead ? 1 : 0) | (e->xcd_remap ? 2 : 0) | (e->small_scan ? 16 : 0);
+    key.payload = job.payload;
     key.options_epoch = e->options_epoch;
     key.stream = e->stream;
     for (const GraphEntry& g : e->graphs) {
         if (g.in == key.in && g.pin == key.pin && g.n == key.n && g.cur == key.cur && g.first == key.first && g.last == key.last &&
-            g.flags == key.flags && g.options_epoch == key.options_epoch && g.stream == key.stream) {
+            g.flags == key.flags && g.payload == key.payload && g.options_epoch == key.options_epoch && g.stream == key.stream) {
             RSX_TRY(hipGraphLaunch(g.exec, e->stream), RSX_CALCULATION_FAILED);
-            e->cur = g.end_cur;
             e->last_in = g.end_last_in;
             e->last_shift = g.end_last_shift;
-            e->result_external = false;
-            e->result_keys = e->keys[e->cur];
-            e->result_perm = e->has_payload ? e->perm[e->cur] : nullptr;
+            finish_chain(e, job, e->keys[g.end_cur]);
             return RSX_OK;
         }
     }
@@ -1240,9 +1212,9 @@ int sort_chain(rsx_engine* e, const void* ext_keys, const uint32_t* ext_perm, ui
     if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
         (void)hipGetLastError();
         e->use_graph = 0;                        // this stream cannot be captured: stay eager from now on
-        return sort_chain_enqueue<Key>(e, ext_keys, ext_perm, count);
+        return sort_chain_passes<Key>(e, job);
     }
-    const int rc = sort_chain_enqueue<Key>(e, ext_keys, ext_perm, count);
+    const int rc = sort_chain_passes<Key>(e, job);
     const hipError_t end = hipStreamEndCapture(e->stream, &graph);
     if (rc != RSX_OK || end != hipSuccess || !graph) {
         if (graph) (void)hipGraphDestroy(graph);
@@ -1263,19 +1235,6 @@ int sort_chain(rsx_engine* e, const void* ext_keys, const uint32_t* ext_perm, ui
     e->graphs.push_back(key);
     RSX_TRY(hipGraphLaunch(exec, e->stream), RSX_CALCULATION_FAILED);
     return RSX_OK;
-}
-
-// sort_chain that carries no payload this time, even on a payload engine (rsx_segmented_unique without positions).  Every chain reads
-// e->has_payload while it ENQUEUES — no kernel does — so the flag is lowered for the duration of the enqueue; the launches are those of
-// an engine created without a payload, and those of every other caller stay what they were.
-template <typename Key>
-int sort_chain_keys_only(rsx_engine* e, const void* ext_keys, uint64_t count)
-{
-    const bool saved = e->has_payload;
-    e->has_payload = false;
-    const int rc = sort_chain<Key>(e, ext_keys, nullptr, count);
-    e->has_payload = saved;
-    return rc;
 }
 
 // a fused-scan workgroup whose poll ran out leaves a flag: surfaced at the host's next synchronisation point
@@ -2090,7 +2049,8 @@ int rsx_sort(rsx_engine* e)
 {
     if (!e) return fail(RSX_CALCULATION_FAILED, "rsx_sort: null engine");
     if (bind_device(e, RSX_CALCULATION_FAILED) != RSX_OK) return RSX_CALCULATION_FAILED;
-    return RSX_BY_KEY(e, sort_chain<uint32_t>(e, nullptr, nullptr, e->n), sort_chain<uint64_t>(e, nullptr, nullptr, e->n));
+    const SortJob job{nullptr, nullptr, e->n, e->first_pass, e->last_pass, e->first_pass, e->last_pass, nullptr, nullptr, e->has_payload};
+    return RSX_BY_KEY(e, sort_chain<uint32_t>(e, job), sort_chain<uint64_t>(e, job));
 }
 
 int rsx_sync(rsx_engine* e)
@@ -2107,14 +2067,18 @@ int rsx_check_status(rsx_engine* e)
     return check_scan_timeout(e, RSX_CALCULATION_FAILED);
 }
 
-int rsx_sort_from(rsx_engine* e, const void* d_keys, const uint32_t* d_payload, uint64_t n)
+extern "C++" {
+namespace {
+
+// rsx_sort_from and rsx_sort_from_to behind their own argument checks: the checks on the input that both share, the alias handling, and
+// the job — passes [first, last) of device input into the engine's buffers, or into d_keys_out / d_payload_out where given.
+int sort_device_input(rsx_engine* e, const void* d_keys, const uint32_t* d_payload, uint64_t n, int first, int last, void* d_keys_out, uint32_t* d_payload_out)
 {
-    if (!e) return fail(RSX_CALCULATION_FAILED, "rsx_sort_from: null engine");
     if (n > e->capacity) return fail(RSX_RESIZE_FAILED, "rsx_sort_from: beyond capacity");
     if (n > 0 && (!d_keys || !aligned16(d_keys))) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_sort_from: keys must be a 16-byte aligned device pointer");
     if (e->has_payload && n > 0 && (!d_payload || !aligned16(d_payload)))
         return fail(RSX_HOST_BUFFERS_FAILED, "rsx_sort_from: payload engine needs a 16-byte aligned payload pointer");
-    if (e->first_pass >= e->last_pass) return fail(RSX_CALCULATION_FAILED, "rsx_sort_from: empty pass range");
+    if (first >= last) return fail(RSX_CALCULATION_FAILED, "rsx_sort_from: empty pass range");
     if (bind_device(e, RSX_CALCULATION_FAILED) != RSX_OK) return RSX_CALCULATION_FAILED;
     if (n == 0) {
         e->n = 0;
@@ -2137,7 +2101,17 @@ int rsx_sort_from(rsx_engine* e, const void* d_keys, const uint32_t* d_payload, 
         d_payload = nullptr;
     }
     e->n = n;
-    return RSX_BY_KEY(e, sort_chain<uint32_t>(e, d_keys, d_payload, n), sort_chain<uint64_t>(e, d_keys, d_payload, n));
+    const SortJob job{d_keys, d_payload, n, first, last, first, last, d_keys_out, d_payload_out, e->has_payload};
+    return RSX_BY_KEY(e, sort_chain<uint32_t>(e, job), sort_chain<uint64_t>(e, job));
+}
+
+}  // namespace
+}  // extern "C++"
+
+int rsx_sort_from(rsx_engine* e, const void* d_keys, const uint32_t* d_payload, uint64_t n)
+{
+    if (!e) return fail(RSX_CALCULATION_FAILED, "rsx_sort_from: null engine");
+    return sort_device_input(e, d_keys, d_payload, n, e->first_pass, e->last_pass, nullptr, nullptr);
 }
 
 int rsx_sort_from_to(rsx_engine* e, const void* d_keys, const uint32_t* d_payload, uint64_t n, int first_pass, int last_pass, void* d_keys_out,
@@ -2155,17 +2129,7 @@ int rsx_sort_from_to(rsx_engine* e, const void* d_keys, const uint32_t* d_payloa
     if (n > 0 && (overlaps(d_keys_out, n * static_cast<uint64_t>(e->key_bytes), d_keys, n * static_cast<uint64_t>(e->key_bytes)) ||
                   (e->has_payload && overlaps(d_payload_out, n * 4, d_payload, n * 4))))
         return fail(RSX_HOST_BUFFERS_FAILED, "rsx_sort_from_to: input and output overlap");
-    const int saved_first = e->first_pass, saved_last = e->last_pass;
-    e->first_pass = first_pass;
-    e->last_pass = last_pass;
-    e->final_keys_out = d_keys_out;
-    e->final_perm_out = d_payload_out;
-    const int rc = rsx_sort_from(e, d_keys, d_payload, n);
-    e->final_keys_out = nullptr;
-    e->final_perm_out = nullptr;
-    e->first_pass = saved_first;
-    e->last_pass = saved_last;
-    return rc;
+    return sort_device_input(e, d_keys, d_payload, n, first_pass, last_pass, d_keys_out, d_payload_out);
 }
 
 int rsx_partition(rsx_engine* e, const void* d_keys, const uint32_t* d_payload, uint64_t n, int shift, int bits, void* d_keys_out,
