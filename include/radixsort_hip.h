@@ -468,6 +468,36 @@ int rsx_segmented_reduce_by_key(rsx_engine* e, const void* d_keys, const void* d
 #define RSX_SCAN_EXCLUSIVE 2   /* flags bit 1: out[i] folds the elements before i only; a restart holds the identity */
 int rsx_segmented_scan(rsx_engine* e, const void* d_keys, const void* d_values, uint64_t n, const uint64_t* d_offsets, uint64_t num_segments,
                        uint32_t flags, uint32_t op, uint32_t value_kind, void* d_values_out);
+/* rsx_segmented_search: lower / upper bound of every query in the sorted segment of the same number (thrust's vectorised binary search;
+ *   torch.searchsorted / bucketize, with ragged rows and in either direction).  Nothing is sorted and nothing is rewritten.
+ *   SEGMENTS.  Haystack segment s is d_sorted[off[s] .. off[s+1]), L_s keys, sorted in the ENGINE's order: its key kind (floats: IEEE 754
+ *   totalOrder) and direction (RSX_OPT_DESCENDING), i.e. what rsx_segmented_sort or rsx_sort_from of an engine of the same kind and
+ *   direction leaves.  Query segment s is d_queries[qoff[s] .. qoff[s+1]) and is searched in haystack segment s.  Keys and queries have the
+ *   engine's key type.
+ *   RESULTS.  For query position j of segment s: d_index_out[j] = #{ i in segment s : key_i strictly before q_j in the engine's order };
+ *   with RSX_SEARCH_RIGHT (flags bit 2) #{ i : key_i not after q_j }.  Both are relative to off[s]; on an ascending engine they are
+ *   lower_bound and upper_bound.  Before and equal are those of the order map: equal means equal by bits, -0.0 is before +0.0, NaNs of
+ *   the same bits are equal and a NaN is an ordinary largest or smallest key.  Positions outside [qoff[0], qoff[S]) are not written.
+ *   OFFSET FORMS.  d_offsets == NULL: one haystack segment [0, n); d_query_offsets must be NULL too and the queries are [0, num_queries).
+ *   d_offsets given, d_query_offsets == NULL: the even form, every segment has Q = num_queries / num_segments queries and query j belongs
+ *   to segment j / Q (rows; a remainder is refused).  Both given: ragged queries, qoff has num_segments + 1 entries in device memory.
+ *   A HAYSTACK THAT IS NOT SORTED gives unspecified results; each still lies in [0, L_s] and nothing outside the buffers is read.
+ *   HOW.  Tiles of 1024 queries, one workgroup each (several tiles above 16 x CUs tiles).  A tile inside one segment of at most 4096 keys
+ *   with at least one query per 16 keys stages the segment in LDS; one inside a longer segment (256 live queries or more) stages 1024
+ *   evenly spaced keys, runs ten levels there and the rest in the window between two samples; every other tile bisects global memory
+ *   (rsx_search.hpp).  Bytes: Q (key + 4), plus per tile L keys (staged), or 1024 sectors and the probed ones.
+ *   THE ENGINE'S SORT STATE IS UNTOUCHED, as with rsx_segmented_scan: n may exceed the capacity and an earlier sort's result stays valid.
+ *   Asynchronous on the engine's stream, nothing read back, every launch sized from n, num_segments and num_queries: capturable.  Offsets
+ *   are validated on the device: with off[s+1] < off[s] or off[S] > n, or the same of qoff against num_queries, NOTHING is written and
+ *   the next rsx_sync / rsx_check_status reports RSX_CALCULATION_FAILED once, naming the first such segment; the engine stays usable.
+ *   REFUSED AT ONCE: RSX_CALCULATION_FAILED for a null engine, unknown flag bits, n or num_queries above 2^31, 2^32 - 1 segments or more,
+ *   a num_queries that is no multiple of num_segments in the even form, d_query_offsets without d_offsets; RSX_HOST_BUFFERS_FAILED for a
+ *   null d_sorted (n > 0), d_queries or d_index_out, a d_sorted that is not 16-byte aligned, queries, output or offsets not aligned to
+ *   their element, the output overlapping an input, anything overlapping the engine's buffers.  num_queries == 0 (or num_segments == 0
+ *   with offsets) launches nothing; n == 0 with queries is valid, every result is 0. */
+#define RSX_SEARCH_RIGHT 4   /* flags bit 2 (disjoint from RSX_UNIQUE_CONSECUTIVE, bit 0, and RSX_SCAN_EXCLUSIVE, bit 1): upper bound */
+int rsx_segmented_search(rsx_engine* e, const void* d_sorted, uint64_t n, const uint64_t* d_offsets, uint64_t num_segments, const void* d_queries,
+                         uint64_t num_queries, const uint64_t* d_query_offsets, uint32_t flags, uint32_t* d_index_out);
 /* Receive buffers other ranks can write to (the peer-store exchange below): rsx_peer_alloc (hipMalloc + an IPC handle to hand to the other
  * PROCESSES, which map it with rsx_peer_open / rsx_peer_close — peer access over xGMI); ranks that are threads of one process use the
  * pointer itself (after rsx_peer_enable, once per other device). */

@@ -40,6 +40,7 @@ UNIQUE_CONSECUTIVE = 1     # RSX_UNIQUE_CONSECUTIVE: flags bit 0 of rsx_segmente
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2                                   # RSX_REDUCE_*: op of rsx_segmented_reduce_by_key
 VALUE_INT32, VALUE_INT64, VALUE_FLOAT32, VALUE_FLOAT64 = 0, 1, 2, 3           # RSX_VALUE_*: its value kinds
 SCAN_EXCLUSIVE = 2         # RSX_SCAN_EXCLUSIVE: flags bit 1 of rsx_segmented_scan
+SEARCH_RIGHT = 4           # RSX_SEARCH_RIGHT: flags bit 2 of rsx_segmented_search
 # rsx_experimental_option (include/radixsort_hip_experiments.h): known to the EXPERIMENTS build only (experiments()); the product library refuses them
 XOPT_DEBUG_RAISE_SCAN_TIMEOUT, XOPT_INLINE_SCAN, XOPT_INLINE_SCAN_MAX_GROUPS, XOPT_REORDER8_KERNEL, XOPT_REORDER8_STAY = 16, 17, 18, 19, 20
 EXPERIMENTS_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tools", "_variants", "libradixsort_hip_experiments.so")
@@ -50,7 +51,7 @@ SYMBOLS = [
     "rsx_create", "rsx_destroy", "rsx_set_stream", "rsx_get_stream", "rsx_set_option", "rsx_get_geometry", "rsx_resize",
     "rsx_upload", "rsx_fill_pad", "rsx_download", "rsx_pin_host", "rsx_unpin_host", "rsx_pipeline_submit", "rsx_pipeline_wait", "rsx_host_device_pointer",
     "rsx_histogram", "rsx_scan", "rsx_paste", "rsx_reorder", "rsx_sort", "rsx_sync", "rsx_check_status",
-    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
+    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
 ]
 
 
@@ -161,6 +162,7 @@ def load_library() -> C.CDLL:
         "rsx_segmented_unique": ([P, P, U64, P, U64, C.c_uint32, P, P, P, P, P], I),
         "rsx_segmented_reduce_by_key": ([P, P, P, U64, P, U64, C.c_uint32, C.c_uint32, C.c_uint32, P, P, P, P], I),
         "rsx_segmented_scan": ([P, P, P, U64, P, U64, C.c_uint32, C.c_uint32, C.c_uint32, P], I),
+        "rsx_segmented_search": ([P, P, U64, P, U64, P, U64, P, C.c_uint32, P], I),
         "rsx_msd_count": ([P, P, U64, I, I, P], I),
         "rsx_msd_scatter": ([P, P, P, U64, P, P], I),
         "rsx_msd_plan": ([P, P, C.c_uint32, C.c_uint32, I, I, P], I),
@@ -505,6 +507,19 @@ class Engine:
         self._check(self.lib.rsx_segmented_scan(
             self._h, C.c_void_p(d_keys) if d_keys else None, C.c_void_p(d_values), n, C.c_void_p(d_offsets) if d_offsets else None, num_segments,
             SCAN_EXCLUSIVE if exclusive else 0, op, value_kind, C.c_void_p(d_values_out)), "rsx_segmented_scan")
+
+    def segmented_search(self, d_sorted: int | None, n: int, d_offsets: int | None, num_segments: int, d_queries: int, num_queries: int,
+                         d_query_offsets: int | None, d_index_out: int, right: bool = False) -> None:
+        """For every query, the number of keys of its haystack segment [off[s], off[s+1]) that come strictly before it in the engine's order
+        (right: that do not come after it) into d_index_out (uint32, relative to off[s]): lower / upper bound on an ascending engine.  The
+        segments must be sorted in the engine's order (key kind, totalOrder for floats, direction).  d_offsets None: one segment [0, n) and
+        the queries [0, num_queries); d_query_offsets None: every segment has num_queries / num_segments queries; else query segment s is
+        [qoff[s], qoff[s+1]).  n may exceed the capacity and the engine's sort result is left alone.  Asynchronous on the engine's stream;
+        bad offsets (nothing is written then) are reported by the next sync() / check_status()."""
+        self._check(self.lib.rsx_segmented_search(
+            self._h, C.c_void_p(d_sorted) if d_sorted else None, n, C.c_void_p(d_offsets) if d_offsets else None, num_segments,
+            C.c_void_p(d_queries) if d_queries else None, num_queries, C.c_void_p(d_query_offsets) if d_query_offsets else None,
+            SEARCH_RIGHT if right else 0, C.c_void_p(d_index_out) if d_index_out else None), "rsx_segmented_search")
 
     # -- exchange step of the sharded sort on the top B <= 8 bits ----------------
     def msd_count(self, d_keys: int, n: int, bits: int, world: int, d_counts: int) -> None:
@@ -1235,3 +1250,130 @@ def cumsum(x, dim: int = -1):
     offsets = None if rows == 1 else torch.arange(0, rows + 1, device=x.device, dtype=torch.int64) * size
     res = _scan_call("cumsum", None, flat, offsets, "sum", False, flat)
     return res.reshape(xm.shape).movedim(-1, dim)
+
+
+# -- search on torch tensors ------------------------------------------------------------------------------------------------------------
+# One small engine per (device, stream, dtype, direction): the search uses none of an engine's capacity-sized buffers, but its order map
+# depends on key kind and direction, so the scan's engines (unsigned, ascending) cannot serve it.
+_SEARCH_ENGINES: dict = {}
+
+
+def _search_engine(device: int, stream: int, dtype_name: str, descending: bool) -> "Engine":
+    key = (device, stream, dtype_name, descending)
+    eng = _SEARCH_ENGINES.get(key)
+    if eng is None:
+        eng = Engine(dtype_name, _SCAN_ENGINE_CAPACITY, payload=False, device=device, descending=descending)
+        eng.set_stream(stream)
+        _SEARCH_ENGINES[key] = eng
+    return eng
+
+
+def _search_call(what: str, hay, offsets, values, value_offsets, right: bool, descending: bool):
+    """One rsx_segmented_search call on 1-D device tensors: the uint32 results as an int32 tensor of values.numel() entries (entries outside
+    [value_offsets[0], value_offsets[-1]) are 0)."""
+    import torch
+    for name, t in (("the sorted keys", hay), ("values", values)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{what}: {name} must be a tensor")
+    name = str(hay.dtype).replace("torch.", "")
+    if name not in _KEY_DTYPES:
+        raise TypeError(f"{what}: unsupported key type {hay.dtype}")
+    if values.dtype != hay.dtype:
+        raise TypeError(f"{what}: values are {values.dtype}, the sorted keys {hay.dtype} (convert one of them: the search compares keys of one type)")
+    if not hay.is_cuda or not values.is_cuda:
+        raise ValueError(f"{what}: the sorted keys and the values must be device tensors (there is no CPU path)")
+    if hay.dim() != 1 or values.dim() != 1 or values.device != hay.device:
+        raise ValueError(f"{what}: the sorted keys and the values must be 1-D tensors on one device")
+    for oname, o in (("offsets", offsets), ("value_offsets", value_offsets)):
+        if o is not None and (o.dtype != torch.int64 or o.dim() != 1 or o.device != hay.device):
+            raise ValueError(f"{what}: {oname} must be a 1-D int64 tensor on the keys' device")
+    if value_offsets is not None and (offsets is None or value_offsets.numel() != offsets.numel()):
+        raise ValueError(f"{what}: value_offsets needs offsets with the same number of entries")
+    n, nq = hay.numel(), values.numel()
+    if n > (1 << 31) or nq > (1 << 31):
+        raise ValueError(f"{what}: at most 2^31 keys and 2^31 values (rsx_segmented_search's bound)")
+    nseg = 1 if offsets is None else max(offsets.numel() - 1, 0)
+    if offsets is not None and value_offsets is None and nseg > 0 and nq % nseg != 0:
+        raise ValueError(f"{what}: without value_offsets every segment has the same number of values, and {nq} is no multiple of {nseg} segments")
+    out = torch.zeros(nq, dtype=torch.int32, device=hay.device)
+    if nq == 0 or nseg == 0:
+        return out
+    k_in = _aligned_copy(hay, torch)
+    q_in = values if values.is_contiguous() else values.contiguous()          # (aligned to its element size either way)
+    offs = []
+    for o in (offsets, value_offsets):
+        offs.append(None if o is None else o if o.is_contiguous() and o.data_ptr() % 8 == 0 else o.clone(memory_format=torch.contiguous_format))
+    dev = hay.device
+    device = dev.index if dev.index is not None else torch.cuda.current_device()
+    eng = _search_engine(device, torch.cuda.current_stream(dev).cuda_stream, name, bool(descending))
+    eng.segmented_search(k_in.data_ptr() if n else None, n, None if offs[0] is None else offs[0].data_ptr(), nseg, q_in.data_ptr(), nq,
+                         None if offs[1] is None else offs[1].data_ptr(), out.data_ptr(), right=bool(right))
+    eng.check_status()      # reports bad offsets of calls that have already finished; no synchronisation
+    return out
+
+
+def segmented_searchsorted(sorted_keys, offsets, values, value_offsets=None, right: bool = False, descending: bool = False):
+    """For every element of the 1-D device tensor `values`, where it would go in its segment of `sorted_keys` in ONE engine call
+    (rsx_segmented_search): the number of keys of segment [offsets[s], offsets[s+1]) that come before it (right=True: that do not come
+    after it), as int64 relative to offsets[s].  value_offsets (int64, like offsets): values[value_offsets[s] : value_offsets[s+1]] are
+    searched in segment s; None: every segment has values.numel() / num_segments values.  The segments must be sorted as this library
+    sorts them (segmented_sort / sort_rows with the same `descending`): floats in IEEE 754 totalOrder, -0.0 before +0.0, NaN an ordinary
+    largest or smallest key.  values must have the keys' dtype.  Never synchronises with the host; bad offsets (nothing is written then)
+    raise RadixSortError at a later call or synchronisation of the engine."""
+    import torch
+    if offsets is None:
+        raise ValueError("segmented_searchsorted: offsets are required (searchsorted takes one segment)")
+    if torch.is_tensor(values) and values.dim() != 1:
+        raise ValueError("segmented_searchsorted: values must be a 1-D tensor")
+    return _search_call("segmented_searchsorted", sorted_keys, offsets, values, value_offsets, right, descending).to(torch.int64).reshape(values.shape)
+
+
+def _search_side(what: str, right: bool, side) -> bool:
+    if side is None:
+        return bool(right)
+    if side not in ("left", "right"):
+        raise ValueError(f"{what}: side must be 'left' or 'right', not {side!r}")
+    if side == "left" and right:
+        raise ValueError(f"{what}: side='left' conflicts with right=True")
+    return side == "right"
+
+
+def searchsorted(sorted_sequence, values, right: bool = False, side=None, out_int32: bool = False, descending: bool = False, sorter=None):
+    """torch.searchsorted(sorted_sequence, values, right=right, side=side, out_int32=out_int32) on device tensors.  A 1-D sorted_sequence
+    takes values of any shape (or a Python scalar); an N-D one takes values whose leading dimensions match, and its rows are the segments
+    of ONE rsx_segmented_search call in the even form.  descending=True searches rows sorted in descending order.  Differences from torch:
+    the rows must be in this library's order, which for floats is IEEE 754 totalOrder (what sort_rows returns): -0.0 sorts before +0.0
+    and NaN is an ordinary largest or smallest key; values must have the sequence's dtype.  Integer dtypes, and floats without -0.0 and
+    NaN, equal torch exactly.  sorter= is not implemented (sort first)."""
+    import torch
+    if sorter is not None:
+        raise NotImplementedError("searchsorted: sorter= is not implemented; sort the sequence first (sort_rows / segmented_sort)")
+    right = _search_side("searchsorted", right, side)
+    if not torch.is_tensor(sorted_sequence):
+        raise TypeError("searchsorted: sorted_sequence must be a tensor")
+    if not torch.is_tensor(values):
+        values = torch.tensor(values, dtype=sorted_sequence.dtype, device=sorted_sequence.device)
+    seq = sorted_sequence
+    if seq.dim() == 0:
+        raise ValueError("searchsorted: sorted_sequence must have at least one dimension")
+    if seq.dim() == 1:
+        res = _search_call("searchsorted", seq, None, values.reshape(-1), None, right, descending).reshape(values.shape)
+    else:
+        if values.dim() != seq.dim() or tuple(values.shape[:-1]) != tuple(seq.shape[:-1]):
+            raise ValueError("searchsorted: the leading dimensions of values must match those of an N-D sorted_sequence")
+        cols = seq.shape[-1]
+        rows = 1
+        for d in seq.shape[:-1]:
+            rows *= d
+        offsets = torch.arange(0, rows + 1, device=seq.device, dtype=torch.int64) * cols
+        res = _search_call("searchsorted", seq.contiguous().reshape(-1), offsets, values.contiguous().reshape(-1), None, right, descending).reshape(values.shape)
+    return res if out_int32 else res.to(torch.int64)
+
+
+def bucketize(input, boundaries, right: bool = False, out_int32: bool = False):
+    """torch.bucketize(input, boundaries, right=right, out_int32=out_int32) on device tensors: for every element of `input` (any shape, or
+    a Python scalar) its bucket among the 1-D ascending `boundaries`.  Order, dtypes and differences from torch as searchsorted."""
+    import torch
+    if torch.is_tensor(boundaries) and boundaries.dim() != 1:
+        raise ValueError("bucketize: boundaries must be a 1-D tensor")
+    return searchsorted(boundaries, input, right=right, out_int32=out_int32)

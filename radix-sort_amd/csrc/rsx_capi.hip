@@ -18,6 +18,7 @@
 #include "rsx_unique.hpp"
 #include "rsx_reduce.hpp"
 #include "rsx_scan_by_key.hpp"
+#include "rsx_search.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -225,6 +226,8 @@ struct rsx_engine {
     // rsx_segmented_reduce_by_key (capi_reduce.inc): all of the above, plus three 8-byte slots per tile: lead, tail and the flags
     uint64_t* red_part = nullptr;
     uint64_t red_part_cap = 0;
+    // rsx_segmented_search (capi_search.inc): no scratch; which path a tile inside one long segment takes
+    int search_sampled = 1;                     // 0: such tiles search global memory directly (env RSX_SEARCH_SAMPLED, for tools/search_bench.py)
 
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -1347,6 +1350,7 @@ const EnvKnob kEnvKnobs[] = {
     {"RSX_R8_EXTRA_LDS_KB", "the same for the 8-bit scatter (-1: per-variant policy)", [](rsx_engine* e, const char* v) { e->r8_extra_lds = kb_or_policy(v, 96); }},
     {"RSX_R8_PACKED", "0: uint32 key and payload travel apart through the 8-bit scatter (default 1: one 64-bit element)", [](rsx_engine* e, const char* v) { e->r8_packed = std::atoi(v) != 0; }},
     {"RSX_R8_WIDE", "8-bit scatter on 512 x 8 (0 / 1, -1: policy = 64-bit keys without payload)", [](rsx_engine* e, const char* v) { e->r8_wide = std::max(-1, std::min(1, std::atoi(v))); }},
+    {"RSX_SEARCH_SAMPLED", "0: rsx_segmented_search bisects long segments in global memory from the first level (default 1: 1024 samples in LDS first)", [](rsx_engine* e, const char* v) { e->search_sampled = std::atoi(v) != 0; }},
 #ifdef RSX_EXPERIMENTS
     {"RSX_ALLOC_MODE", "experiments: key buffers as VMM chunks mapped in creation (1) or shuffled (2) order", [](rsx_engine* e, const char* v) { e->alloc_mode = std::max(0, std::min(2, std::atoi(v))); }},
     {"RSX_ALLOC_CHUNK_MB", "experiments: chunk size of RSX_ALLOC_MODE", [](rsx_engine* e, const char* v) { e->alloc_chunk = static_cast<size_t>(std::max(0, std::atoi(v))) << 20; }},
@@ -2377,6 +2381,7 @@ int rsx_peer_enable(rsx_engine* e, int peer_device)
 #include "capi_unique.inc"
 #include "capi_reduce.inc"
 #include "capi_scan.inc"
+#include "capi_search.inc"
 
 int rsx_key_range(rsx_engine* e, const void* d_keys, uint64_t n, uint64_t* lo, uint64_t* hi)
 {
