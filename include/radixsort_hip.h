@@ -498,6 +498,46 @@ int rsx_segmented_scan(rsx_engine* e, const void* d_keys, const void* d_values, 
 #define RSX_SEARCH_RIGHT 4   /* flags bit 2 (disjoint from RSX_UNIQUE_CONSECUTIVE, bit 0, and RSX_SCAN_EXCLUSIVE, bit 1): upper bound */
 int rsx_segmented_search(rsx_engine* e, const void* d_sorted, uint64_t n, const uint64_t* d_offsets, uint64_t num_segments, const void* d_queries,
                          uint64_t num_queries, const uint64_t* d_query_offsets, uint32_t flags, uint32_t* d_index_out);
+/* rsx_segmented_compact: stream compaction of every segment by a byte mask or by one key bound per segment (thrust::copy_if, CUB's
+ *   DeviceSelect::Flagged and DevicePartition; torch.masked_select, x[mask] and nonzero, with ragged rows and their new offsets).  Nothing is
+ *   sorted.  (The name is compact: rsx_partition* is the digit partition of the sharded sort.)
+ *   PREDICATE.  Exactly one of d_mask and d_bounds is given.  Mask form: element i is kept iff d_mask[i] != 0 (n bytes, any non-zero value,
+ *   no alignment: torch.bool and uint8 as they are); the keys are opaque bits of the engine's key width.  Bound form: d_bounds holds one key
+ *   of the engine's key type per segment; key k of segment s is kept iff it does not come after d_bounds[s] in the ENGINE's order (key
+ *   kind, IEEE 754 totalOrder for floats, direction), with RSX_COMPACT_STRICT iff it comes strictly before: an ascending engine keeps
+ *   k <= b, a descending float engine k >= b.  -0.0 comes before +0.0 and a NaN is an ordinary key.  RSX_COMPACT_INVERT keeps what the
+ *   predicate rejects, in either form.
+ *   COMPACT MODE (default).  With K(i) the number of kept elements in [off[0], i): a kept element i of segment s goes to d_keys_out[K(i)],
+ *   bits unchanged, and its position relative to off[s] to d_index_out[K(i)].  d_kept_offsets_out[s] = K(off[s]) (num_segments + 1
+ *   uint64): koff[0] = 0, koff[s+1] - koff[s] elements of segment s were kept, koff[S] is the total.  The packing is dense across the
+ *   segments, as rsx_segmented_unique's; entries past koff[S] are not written.
+ *   PARTITION MODE (RSX_COMPACT_PARTITION).  Nothing is dropped and the outputs cover the input's index range, as rsx_segmented_sort's:
+ *   within [off[s], off[s+1]) the kept elements come first and the rejected ones behind them, both in input order (stable on both
+ *   sides); d_index_out[off[s] + j] is the position, relative to off[s], that the element now at off[s] + j came from; koff is the
+ *   same, the split point of segment s is off[s] + koff[s+1] - koff[s].  Positions outside [off[0], off[S]) are not written.
+ *   BOTH MODES.  d_keys_out and d_index_out may each be NULL; with both NULL the call only counts.  d_kept_offsets_out is required.
+ *   In mask form the keys are read only for d_keys_out: with d_keys_out == NULL d_keys is checked (non-null, 16-byte aligned) and not read.
+ *   d_offsets == NULL is ONE segment [0, n).  The output is a function of the inputs alone: no atomic decides a destination.
+ *   HOW.  The global grid of 4096-element tiles, reduce-then-scan: the kept elements per tile, the table scan of the sort family, the kept
+ *   offsets, then a pass that recomputes the predicate, ranks the survivors of a tile, stages them in LDS at their rank and stores the
+ *   staged copy to consecutive addresses (rsx_compact.hpp).  Bytes: the predicate's input twice (n mask bytes, or n keys), n keys once
+ *   more in mask form, and what is kept.
+ *   THE ENGINE'S SORT STATE IS UNTOUCHED, as with rsx_segmented_scan: n may exceed the capacity and an earlier sort's result stays valid;
+ *   only per-tile scratch grows, outside stream captures.  Asynchronous on the engine's stream, nothing read back, every launch sized from
+ *   n and num_segments: capturable.  n == 0 (or num_segments == 0 with offsets) launches and writes nothing.  Offsets are validated on
+ *   the device: with off[s+1] < off[s] or off[s+1] > n every kernel leaves at once, d_kept_offsets_out is all zeros, d_keys_out and
+ *   d_index_out are not written, and the next rsx_sync / rsx_check_status reports RSX_CALCULATION_FAILED once, naming the first such
+ *   segment; the engine stays usable.
+ *   REFUSED AT ONCE: RSX_CALCULATION_FAILED for a null engine, unknown flag bits, both or neither of d_mask and d_bounds,
+ *   RSX_COMPACT_STRICT with a mask, n above 2^31, 2^32 - 1 segments or more; RSX_HOST_BUFFERS_FAILED for a d_keys that is null or not
+ *   16-byte aligned, a null d_kept_offsets_out, outputs or bounds not aligned to their element, offsets or koff not 8-byte aligned, any
+ *   overlap between an output and an input or another output (no operation is in place), anything overlapping the engine's buffers. */
+#define RSX_COMPACT_PARTITION 8    /* flags bit 3: nothing is dropped; in every segment the kept elements come first, the others behind them, both in input order */
+#define RSX_COMPACT_INVERT 16      /* flags bit 4: keep what the predicate rejects */
+#define RSX_COMPACT_STRICT 32      /* flags bit 5, bound form only: keep keys strictly before the bound */
+int rsx_segmented_compact(rsx_engine* e, const void* d_keys, uint64_t n, const uint64_t* d_offsets /* or NULL */, uint64_t num_segments,
+                          const uint8_t* d_mask /* or NULL */, const void* d_bounds /* or NULL */, uint32_t flags,
+                          void* d_keys_out /* or NULL */, uint32_t* d_index_out /* or NULL */, uint64_t* d_kept_offsets_out);
 /* Receive buffers other ranks can write to (the peer-store exchange below): rsx_peer_alloc (hipMalloc + an IPC handle to hand to the other
  * PROCESSES, which map it with rsx_peer_open / rsx_peer_close — peer access over xGMI); ranks that are threads of one process use the
  * pointer itself (after rsx_peer_enable, once per other device). */

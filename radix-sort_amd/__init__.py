@@ -41,6 +41,7 @@ REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2                                   #
 VALUE_INT32, VALUE_INT64, VALUE_FLOAT32, VALUE_FLOAT64 = 0, 1, 2, 3           # RSX_VALUE_*: its value kinds
 SCAN_EXCLUSIVE = 2         # RSX_SCAN_EXCLUSIVE: flags bit 1 of rsx_segmented_scan
 SEARCH_RIGHT = 4           # RSX_SEARCH_RIGHT: flags bit 2 of rsx_segmented_search
+COMPACT_PARTITION, COMPACT_INVERT, COMPACT_STRICT = 8, 16, 32                  # RSX_COMPACT_*: flags bits 3, 4, 5 of rsx_segmented_compact
 # rsx_experimental_option (include/radixsort_hip_experiments.h): known to the EXPERIMENTS build only (experiments()); the product library refuses them
 XOPT_DEBUG_RAISE_SCAN_TIMEOUT, XOPT_INLINE_SCAN, XOPT_INLINE_SCAN_MAX_GROUPS, XOPT_REORDER8_KERNEL, XOPT_REORDER8_STAY = 16, 17, 18, 19, 20
 EXPERIMENTS_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tools", "_variants", "libradixsort_hip_experiments.so")
@@ -51,7 +52,7 @@ SYMBOLS = [
     "rsx_create", "rsx_destroy", "rsx_set_stream", "rsx_get_stream", "rsx_set_option", "rsx_get_geometry", "rsx_resize",
     "rsx_upload", "rsx_fill_pad", "rsx_download", "rsx_pin_host", "rsx_unpin_host", "rsx_pipeline_submit", "rsx_pipeline_wait", "rsx_host_device_pointer",
     "rsx_histogram", "rsx_scan", "rsx_paste", "rsx_reorder", "rsx_sort", "rsx_sync", "rsx_check_status",
-    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
+    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
 ]
 
 
@@ -163,6 +164,7 @@ def load_library() -> C.CDLL:
         "rsx_segmented_reduce_by_key": ([P, P, P, U64, P, U64, C.c_uint32, C.c_uint32, C.c_uint32, P, P, P, P], I),
         "rsx_segmented_scan": ([P, P, P, U64, P, U64, C.c_uint32, C.c_uint32, C.c_uint32, P], I),
         "rsx_segmented_search": ([P, P, U64, P, U64, P, U64, P, C.c_uint32, P], I),
+        "rsx_segmented_compact": ([P, P, U64, P, U64, P, P, C.c_uint32, P, P, P], I),
         "rsx_msd_count": ([P, P, U64, I, I, P], I),
         "rsx_msd_scatter": ([P, P, P, U64, P, P], I),
         "rsx_msd_plan": ([P, P, C.c_uint32, C.c_uint32, I, I, P], I),
@@ -520,6 +522,23 @@ class Engine:
             self._h, C.c_void_p(d_sorted) if d_sorted else None, n, C.c_void_p(d_offsets) if d_offsets else None, num_segments,
             C.c_void_p(d_queries) if d_queries else None, num_queries, C.c_void_p(d_query_offsets) if d_query_offsets else None,
             SEARCH_RIGHT if right else 0, C.c_void_p(d_index_out) if d_index_out else None), "rsx_segmented_search")
+
+    def segmented_compact(self, d_keys: int, n: int, d_offsets: int | None, num_segments: int, d_mask: int | None, d_bounds: int | None,
+                          d_keys_out: int | None, d_index_out: int | None, d_kept_offsets_out: int, partition: bool = False, invert: bool = False,
+                          strict: bool = False) -> None:
+        """Stream compaction of every segment [off[s], off[s+1]): element i is kept iff d_mask[i] != 0 (one byte per element), or - d_bounds,
+        one key per segment - iff its key does not come after the segment's bound in the engine's order (strict: comes strictly before);
+        invert keeps the others.  The kept elements go densely packed, in input order, to d_keys_out, their positions relative to off[s]
+        to d_index_out (uint32), and d_kept_offsets_out (num_segments + 1 uint64) gets the number kept before every segment.  partition:
+        nothing is dropped; every segment is rewritten in place of its index range, kept elements first, both sides in input order.
+        Either output may be None (both: count only).  d_offsets None: ONE segment [0, n).  n may exceed the capacity and the engine's
+        sort result is left alone.  Asynchronous on the engine's stream; bad offsets (the kept offsets are zeros then, nothing else is
+        written) are reported by the next sync() / check_status()."""
+        flags = (COMPACT_PARTITION if partition else 0) | (COMPACT_INVERT if invert else 0) | (COMPACT_STRICT if strict else 0)
+        opt = lambda p: C.c_void_p(p) if p else None
+        self._check(self.lib.rsx_segmented_compact(
+            self._h, opt(d_keys), n, opt(d_offsets), num_segments, opt(d_mask), opt(d_bounds), flags, opt(d_keys_out), opt(d_index_out),
+            opt(d_kept_offsets_out)), "rsx_segmented_compact")
 
     # -- exchange step of the sharded sort on the top B <= 8 bits ----------------
     def msd_count(self, d_keys: int, n: int, bits: int, world: int, d_counts: int) -> None:
@@ -1377,3 +1396,166 @@ def bucketize(input, boundaries, right: bool = False, out_int32: bool = False):
     if torch.is_tensor(boundaries) and boundaries.dim() != 1:
         raise ValueError("bucketize: boundaries must be a 1-D tensor")
     return searchsorted(boundaries, input, right=right, out_int32=out_int32)
+
+
+# -- compaction on torch tensors --------------------------------------------------------------------------------------------------------
+def _compact_keys_check(what: str, keys) -> str:
+    """the key type first (TypeError), then the device (ValueError): the name of the dtype"""
+    import torch
+    if not torch.is_tensor(keys):
+        raise TypeError(f"{what}: the input must be a tensor")
+    name = str(keys.dtype).replace("torch.", "")
+    if name not in _KEY_DTYPES:
+        raise TypeError(f"{what}: unsupported key type {keys.dtype}")
+    if not keys.is_cuda:
+        raise ValueError(f"{what}: the input must be a device tensor (there is no CPU path)")
+    return name
+
+
+def _compact_call(what: str, keys, offsets, mask, bounds, strict: bool, invert: bool, descending: bool, partition: bool, want_keys: bool,
+                  want_index: bool):
+    """One rsx_segmented_compact call on a 1-D device tensor (offsets None: one segment).  Returns (values, kept_offsets, index): compact
+    mode trims values and index to kept_offsets[-1] (ONE host synchronisation); partition mode returns them whole and reads nothing back."""
+    import torch
+    name = _compact_keys_check(what, keys)
+    if (mask is None) == (bounds is None):
+        raise ValueError(f"{what}: exactly one of mask and bound must be given")
+    if mask is not None:
+        if strict:
+            raise ValueError(f"{what}: strict belongs to the bound form (a mask has no ties)")
+        if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"{what}: the mask must be a torch.bool or torch.uint8 tensor")
+        if mask.device != keys.device or mask.shape != keys.shape:
+            raise ValueError(f"{what}: the mask must be on the keys' device and of the keys' shape")
+    n = keys.numel()
+    if n > (1 << 31):
+        raise ValueError(f"{what}: at most 2^31 elements (rsx_segmented_compact's bound)")
+    nseg = 1 if offsets is None else max(offsets.numel() - 1, 0)
+    if bounds is not None:
+        if not torch.is_tensor(bounds) or bounds.dtype != keys.dtype:
+            raise TypeError(f"{what}: the bound must be a tensor of the keys' dtype {keys.dtype}")
+        if bounds.device != keys.device or bounds.numel() != nseg:
+            raise ValueError(f"{what}: the bound must be on the keys' device and hold one key per segment ({nseg})")
+    dev = keys.device
+    kept = torch.zeros(nseg + 1, dtype=torch.int64, device=dev)
+    # partition mode writes only [offsets[0], offsets[-1]): the rest of the outputs is the input's keys and zeros
+    values = (keys.reshape(-1).clone() if partition else torch.empty(n, dtype=keys.dtype, device=dev)) if want_keys else None
+    index = (torch.zeros if partition else torch.empty)(n, dtype=torch.int32, device=dev) if want_index else None
+    total = n
+    if n > 0 and nseg > 0:
+        k_in = _aligned_copy(keys, torch)
+        off = None
+        if offsets is not None:
+            off = offsets if offsets.is_contiguous() and offsets.data_ptr() % 8 == 0 else offsets.clone(memory_format=torch.contiguous_format)
+        m_in = None if mask is None else mask if mask.is_contiguous() else mask.contiguous()
+        b_in = None if bounds is None else bounds.contiguous().reshape(-1)
+        device = dev.index if dev.index is not None else torch.cuda.current_device()
+        eng = _search_engine(device, torch.cuda.current_stream(dev).cuda_stream, name, bool(descending))
+        eng.segmented_compact(k_in.data_ptr(), n, off.data_ptr() if off is not None else None, nseg, m_in.data_ptr() if m_in is not None else None,
+                              b_in.data_ptr() if b_in is not None else None, values.data_ptr() if want_keys else None,
+                              index.data_ptr() if want_index else None, kept.data_ptr(), partition=partition, invert=invert, strict=strict)
+        if not partition:
+            total = int(kept[-1].item())            # the one read-back (a host synchronisation): how many were kept
+        eng.check_status()      # reports bad offsets of calls that have already finished
+    elif not partition:
+        total = 0
+    widen = lambda t: None if t is None else (t.to(torch.int64) & 0xFFFFFFFF)
+    return (None if values is None else values[:total]), kept, widen(None if index is None else index[:total])
+
+
+def segmented_compact(keys, offsets, mask=None, bound=None, strict: bool = False, invert: bool = False, descending: bool = False,
+                      partition: bool = False, return_index: bool = False):
+    """Stream compaction of every segment [offsets[s], offsets[s+1]) of the 1-D device tensor `keys` in ONE engine call
+    (rsx_segmented_compact): returns (values, kept_offsets, [index]).  mask (torch.bool / uint8, keys' shape): element i is kept iff
+    mask[i] != 0.  bound (keys' dtype, one per segment): a key is kept iff it does not come after its segment's bound in this library's
+    order - k <= bound ascending, k >= bound with descending=True; strict=True drops the ties; floats compare in IEEE 754 totalOrder
+    (-0.0 before +0.0, NaN an ordinary largest or smallest key).  invert=True keeps what the predicate rejects.  values holds the kept
+    keys of segment s, in input order, at [kept_offsets[s], kept_offsets[s+1]); index (int64) their positions relative to offsets[s].
+    values and index are trimmed to kept_offsets[-1], which reads one int64 back: one host synchronisation per call.  partition=True
+    drops nothing: values and index are shaped like keys, every segment holds its kept elements first and the others behind them, both in
+    input order, kept_offsets[s+1] - kept_offsets[s] is the split of segment s, positions outside [offsets[0], offsets[-1]) hold the
+    input's keys and index 0, and nothing is read back.  Bad offsets raise RadixSortError."""
+    import torch
+    _compact_keys_check("segmented_compact", keys)
+    if keys.dim() != 1:
+        raise ValueError("segmented_compact: keys must be a 1-D device tensor")
+    if offsets is not None and (offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.device != keys.device):
+        raise ValueError("segmented_compact: offsets must be a 1-D int64 tensor on the keys' device (or None: one segment)")
+    v, ko, idx = _compact_call("segmented_compact", keys, offsets, mask, bound, strict, invert, descending, partition, True, return_index)
+    return (v, ko) + ((idx,) if return_index else ())
+
+
+def masked_select(x, mask):
+    """torch.masked_select(x, mask) on device tensors: the elements of x where mask (torch.bool or uint8, broadcastable with x) is set,
+    in row-major order, 1-D.  The call moves bits: NaNs and -0.0 come back as they went in.  One host synchronisation (the length)."""
+    import torch
+    if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8):
+        raise TypeError("masked_select: the mask must be a torch.bool or torch.uint8 tensor")
+    _compact_keys_check("masked_select", x)
+    if not mask.is_cuda:
+        raise ValueError("masked_select: x and mask must be device tensors (there is no CPU path)")
+    xb, mb = torch.broadcast_tensors(x, mask)
+    v, _, _ = _compact_call("masked_select", xb.contiguous().reshape(-1), None, mb.contiguous().reshape(-1), None, False, False, False, False, True, False)
+    return v
+
+
+def nonzero(x, as_tuple: bool = False):
+    """torch.nonzero(x, as_tuple=as_tuple) on a device tensor: the indices of the elements that differ from zero (-0.0 is zero, NaN is
+    not), int64, in row-major order.  The mask x != 0 is compacted with positions only and the flat positions are unravelled on the
+    device.  At most 2^31 elements.  One host synchronisation (the length)."""
+    import torch
+    if not torch.is_tensor(x):
+        raise TypeError("nonzero: x must be a tensor")
+    if not x.is_cuda:
+        raise ValueError("nonzero: x must be a device tensor (there is no CPU path)")
+    if x.numel() > (1 << 31):
+        raise ValueError("nonzero: at most 2^31 elements (rsx_segmented_compact's bound)")
+    flat_mask = (x != 0).contiguous().reshape(-1)
+    # positions only: in mask form without a key output the call does not read the keys, so the (16-byte aligned) mask stands in for them
+    flat_mask = _aligned_copy(flat_mask, torch)
+    idx = torch.empty(flat_mask.numel(), dtype=torch.int32, device=x.device)
+    kept = torch.zeros(2, dtype=torch.int64, device=x.device)
+    total = 0
+    if flat_mask.numel() > 0:
+        dev = x.device
+        device = dev.index if dev.index is not None else torch.cuda.current_device()
+        eng = _search_engine(device, torch.cuda.current_stream(dev).cuda_stream, "uint32", False)
+        eng.segmented_compact(flat_mask.data_ptr(), flat_mask.numel(), None, 1, flat_mask.data_ptr(), None, None, idx.data_ptr(), kept.data_ptr())
+        total = int(kept[-1].item())                # the one read-back (a host synchronisation): how many there are
+        eng.check_status()
+    idx = idx[:total].to(torch.int64) & 0xFFFFFFFF
+    cols = []
+    rem = idx
+    for size in reversed(x.shape):
+        cols.append(rem % size)
+        rem = torch.div(rem, size, rounding_mode="floor")
+    cols.reverse()
+    if as_tuple:
+        return tuple(cols) if cols else (idx,)
+    return torch.stack(cols, dim=1) if cols else idx.new_zeros((idx.numel(), 0))
+
+
+def compact_rows(x, mask=None, bound=None, strict: bool = False, invert: bool = False, descending: bool = False, return_index: bool = False):
+    """The ragged result of filtering a padded batch: the rows of x along its last dimension are the segments of ONE rsx_segmented_compact
+    call.  mask: shaped like x (or broadcastable to it); bound: one key per row, shaped like x without its last dimension (or a scalar
+    tensor for all rows).  Returns (values, row_offsets, [index]): row r's survivors are values[row_offsets[r] : row_offsets[r+1]], in
+    input order; index (int64) their columns.  strict / invert / descending as segmented_compact."""
+    import torch
+    _compact_keys_check("compact_rows", x)
+    if x.dim() == 0:
+        raise ValueError("compact_rows: x must be a device tensor with at least one dimension")
+    cols = x.shape[-1]
+    rows = x.numel() // cols if cols else 0
+    offsets = torch.arange(0, rows + 1, device=x.device, dtype=torch.int64) * cols
+    flat = x.contiguous().reshape(-1)
+    m = b = None
+    if mask is not None:
+        if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError("compact_rows: the mask must be a torch.bool or torch.uint8 tensor")
+        m = mask.expand(x.shape).contiguous().reshape(-1)
+    if bound is not None:
+        if not torch.is_tensor(bound):
+            raise TypeError("compact_rows: the bound must be a tensor of x's dtype")
+        b = bound.expand(x.shape[:-1]).contiguous().reshape(-1)
+    v, ko, idx = _compact_call("compact_rows", flat, offsets, m, b, strict, invert, descending, False, True, return_index)
+    return (v, ko) + ((idx,) if return_index else ())

@@ -19,6 +19,7 @@
 #include "rsx_reduce.hpp"
 #include "rsx_scan_by_key.hpp"
 #include "rsx_search.hpp"
+#include "rsx_compact.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -2382,6 +2383,7 @@ int rsx_peer_enable(rsx_engine* e, int peer_device)
 #include "capi_reduce.inc"
 #include "capi_scan.inc"
 #include "capi_search.inc"
+#include "capi_compact.inc"
 
 int rsx_key_range(rsx_engine* e, const void* d_keys, uint64_t n, uint64_t* lo, uint64_t* hi)
 {
