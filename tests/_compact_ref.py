@@ -12,6 +12,7 @@ the kept elements in [off[0], i):
 
   compact_oracle   numpy, vectorised
   compact_loop     a plain loop over the elements (small inputs)
+  compact_tiled    the kernels' own arithmetic tile by tile, with three named slips in what a workgroup carries between tiles
 Both return (keys_out, index_out, koff, written): arrays of n entries, `written` marking the positions the call must write (every other
 position must keep what it held).
 
@@ -137,6 +138,131 @@ def tile_facts(n, off, keep=None):
     return spans, kept
 
 
+def workgroups(n, cus=256):
+    """the tiles of every workgroup of compact_write_kernel: [[t, t + 1, ...], ...], `chunk` consecutive tiles each"""
+    tiles, _, chunk, _ = grid(n, cus)
+    return [list(range(t0, min(t0 + chunk, tiles))) for t0 in range(0, tiles, chunk)]
+
+
+# -- the kernels' arithmetic, tile by tile -------------------------------------------------------------------------------------------------
+
+FAULTS = ("gallop", "boundary", "stale_stage")
+LAST_WAVE = (THREADS - 64) * (TILE // THREADS)          # the tile position of the first element of the workgroup's last wave
+
+
+def _seg_upper(o, start, x):
+    """compact_seg_upper: the first s in [start, S] with off[s] > x, S + 1 if there is none"""
+    return start + int(np.searchsorted(o[start:], x, side="right"))
+
+
+def compact_tiled(keys, off, mask=None, bounds=None, descending=False, strict=False, invert=False, partition=False, cus=256, fault=None):
+    """The arithmetic that the top of radix-sort_amd/csrc/rsx_compact.hpp documents, numpy per tile and a plain loop over the tiles:
+      count   per workgroup a gallop start carried from tile to tile (`start`, `wstart`); per tile the live range [a, e), the segments of
+              a and of e - 1, the segment of every live element between those two, the kept count -> table[tile]; for every off[s] inside
+              the tile the kept elements of the tile before it -> koff[s]
+      scan    the flat exclusive scan of the table; koff[s] += table[off[s] >> 12]
+      write   per tile again: K(i) = table[tile] + rank; compact mode and a partition tile inside one segment stage in LDS by rank and
+              leave as one or two runs, a partition tile that spans segments stores per element by the partition formula
+    and returns what compact_oracle returns.  With fault=None the two are equal on every layout here (tests/test_compact.py).
+
+    Three named faults, each a slip in what a workgroup carries from tile to tile, to show which layouts would notice:
+      "gallop"       a workgroup's second and later tiles start their segment search one segment too far
+      "boundary"     an offset equal to a tile's start is counted by the tile before it (all of that tile's kept elements lie before
+                     it), while the scanned table entry added to it stays that of its own tile
+      "stale_stage"  in a workgroup's second and later tiles the copy-out does not wait for the staging stores of the workgroup's last
+                     wave: those slots still hold what the tile before staged there (zeros where it staged nothing)"""
+    assert fault is None or fault in FAULTS
+    n = keys.size
+    o = _offsets(n, off)
+    S = o.size - 1
+    lo, hi = int(o[0]), int(o[-1])
+    tiles, npad, chunk, _ = grid(n, cus)
+    k = order_map(keys, descending)
+    b = None if bounds is None else order_map(np.asarray(bounds, dtype=keys.dtype), descending)
+    m = None if mask is None else np.asarray(mask).view(np.uint8)
+    assert (m is None) != (b is None) and not (m is not None and strict)
+
+    def tile(t, start, later):
+        """(a, e, segment of every live element, keep flags, the next gallop start), or None for a tile without a live element"""
+        a, e = max(t * TILE, lo), min((t + 1) * TILE, hi)
+        if a >= e:
+            return None
+        if fault == "gallop" and later:
+            start = min(start + 1, S)                             # (clipped to the last segment: the mirror stays inside the offsets)
+        s_first = _seg_upper(o, start, a) - 1
+        s_last = _seg_upper(o, s_first + 1, e - 1) - 1
+        i = np.arange(a, e, dtype=np.int64)
+        seg = s_first + np.maximum(np.searchsorted(o[s_first:s_last + 1], i, side="right") - 1, 0)       # search_segment_of in [s_first, s_last]
+        if m is not None:
+            keep = m[a:e] != 0
+        else:
+            keep = (k[a:e] < b[seg]) if strict else (k[a:e] <= b[seg])
+        return a, e, seg, (~keep if invert else keep), s_last + 1
+
+    # count
+    table = np.zeros(npad, dtype=np.int64)
+    koff = np.zeros(S + 1, dtype=np.int64)
+    for t0 in range(0, tiles + 1, chunk):
+        start = wstart = 0
+        for t in range(t0, min(t0 + chunk, tiles + 1)):
+            before = np.zeros(TILE + 1, dtype=np.int64)           # kept elements of the tile before tile position x
+            got = tile(t, start, t > t0)
+            if got is not None:
+                a, e, _, keep, start = got
+                before[a - t * TILE + 1:e - t * TILE + 1] = np.cumsum(keep)
+                before[e - t * TILE + 1:] = before[e - t * TILE]
+            table[t] = before[TILE]
+            edge = fault == "boundary"                            # (then the tile owns (start, start + 4096], not [start, start + 4096))
+            wstart = _seg_upper(o, wstart, t * TILE - (0 if edge else 1)) if t else 0
+            s_end = wstart + int(np.searchsorted(o[wstart:], (t + 1) * TILE, side="right" if edge else "left"))
+            own = np.arange(wstart, s_end)
+            koff[own] = before[o[own] - t * TILE]
+    # scan
+    scanned = np.concatenate([[0], np.cumsum(table)[:-1]])
+    koff += scanned[o >> 12]
+    # write
+    keys_out, index_out, written = np.zeros(n, dtype=keys.dtype), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=bool)
+
+    def store(d, kk, ii):
+        keys_out[d], index_out[d], written[d] = kk, ii, True
+
+    for t0 in range(0, tiles, chunk):
+        start = 0
+        skey, sidx = np.zeros(TILE, dtype=keys.dtype), np.zeros(TILE, dtype=np.int64)        # the staging area: what the tile before left
+        for t in range(t0, min(t0 + chunk, tiles)):
+            got = tile(t, start, t > t0)
+            if got is None:
+                continue
+            a, e, seg, keep, start = got
+            i = np.arange(a, e, dtype=np.int64)
+            rank = np.cumsum(keep) - keep
+            total = int(keep.sum())
+            tbase = int(scanned[t])
+            rel = i - o[seg]
+            if not partition or seg[0] == seg[-1]:
+                slot = np.where(keep, rank, total + (i - a) - rank)
+                put = keep.copy() if not partition else np.ones(e - a, dtype=bool)
+                if fault == "stale_stage" and t > t0:
+                    put &= i - t * TILE < LAST_WAVE
+                skey[slot[put]], sidx[slot[put]] = keys[a:e][put], rel[put]
+                count = e - a if partition else total
+                r = np.arange(count)
+                if partition:
+                    s0 = int(seg[0])
+                    k0, kept_s = int(koff[s0]), int(koff[s0 + 1] - koff[s0])
+                    dk = int(o[s0]) + (tbase - k0)
+                    dr = int(o[s0]) + kept_s + (a - int(o[s0])) - (tbase - k0)
+                    d = np.where(r < total, dk + r, dr + (r - total))
+                else:
+                    d = tbase + r
+                store(d, skey[:count], sidx[:count])
+            else:
+                kb = tbase + rank - koff[seg]                     # kept before i in its segment
+                kept_s = koff[seg + 1] - koff[seg]
+                store(o[seg] + np.where(keep, kb, kept_s + rel - kb), keys[a:e], rel)
+    return keys_out, index_out, koff, written
+
+
 # -- the layouts of tests/test_gpu_compact.py -------------------------------------------------------------------------------------------------
 
 def offsets_from(lengths, start=0):
@@ -193,6 +319,50 @@ def empties_layout():
 def mid_tile_layout():
     """(n, off): off[0] and off[S] in the middle of a tile, tiles before and after that hold no live element"""
     return 5 * TILE, np.array([TILE + 1000, TILE + 1000 + 700, 3 * TILE + 50], dtype=np.uint64)
+
+
+def burst(count):
+    """`count` short segment lengths cycling through 0, 1, 2, 15, 16, 17, 0, 3 (54 elements a cycle: thread, vector and empty edges)"""
+    return [(0, 1, 2, 15, 16, 17, 0, 3)[i % 8] for i in range(count)]
+
+
+def walk_layout(cus=256):
+    """(n, off): 4096 x 16 x CUs + 4096 + 5 elements, so that a workgroup walks two tiles (2w and 2w + 1) on a device of `cus` CUs, and
+    1322 segments placed for what a workgroup carries from its first tile to its second (tests/test_compact.py asserts each from the
+    layout alone).  With T = 4096:
+      off[0] = 3T + 1000        workgroup 0 dead; workgroup 1 = (dead, live inside one segment with a dead front)
+      a segment to 4T
+      600 short segments        in tile 4, the first of workgroup 2: the gallop of tile 5 starts beyond 600
+      a segment to 5T           ends on the edge between the two tiles of workgroup 2
+      300 offsets equal to 5T   empty segments exactly at the start of a workgroup's second tile
+      400 short segments        more than 256 offsets inside that second tile
+      a segment to 6T + 123, one to 9T + 623     workgroup 3 = (spans segments, inside one), workgroup 4 = (inside one, spans segments)
+      a segment to (tiles - 24) T + 77           covers whole workgroups
+      LENGTHS
+      a segment to (tiles - 4) T + 2000          off[S] in the first tile of a workgroup: (live, dead); the next workgroup is dead"""
+    T = TILE
+    n = T * 16 * cus + T + 5
+    tiles = grid(n, cus)[0]
+    ends = [4 * T]
+    pos = 4 * T
+    for L in burst(600):
+        pos += L
+        ends.append(pos)
+    assert pos < 5 * T
+    ends += [5 * T] * 301
+    pos = 5 * T
+    for L in burst(400):
+        pos += L
+        ends.append(pos)
+    assert pos < 6 * T
+    ends += [6 * T + 123, 9 * T + 623, (tiles - 24) * T + 77]
+    pos = ends[-1]
+    for L in LENGTHS:
+        pos += L
+        ends.append(pos)
+    assert pos < (tiles - 4) * T
+    ends.append((tiles - 4) * T + 2000)
+    return n, np.array([3 * T + 1000] + ends, dtype=np.uint64)
 
 
 def nothing_layout():

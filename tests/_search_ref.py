@@ -13,7 +13,8 @@ the even form, Q / S queries per segment; both given = ragged queries.  Position
 The grid: tiles of TILE_Q = 1024 consecutive query positions, 256 threads; above 16 x CUs tiles a workgroup walks
 ceil(tiles / (16 x CUs)) of them.  A tile whose live queries lie in one segment of L keys is RESIDENT when L <= 4096 and 16 Qt >= L,
 SAMPLED when L > 4096 and Qt >= 256 (Qt = live queries of the tile), DIRECT otherwise and whenever it spans several segments.  The sampled
-path stages the SAMPLES = 1024 keys at sample_positions(L) = floor(i L / 1024), i = 0 .. 1023.
+path stages the SAMPLES = 1024 keys at sample_positions(L) = floor(i L / 1024), i = 0 .. 1023.  tile_walk gives the (path, staged segment)
+of every tile of every workgroup; the layouts at the end are those of tests/test_gpu_search_paths.py.
 """
 import numpy as np
 
@@ -106,6 +107,63 @@ def tile_paths(n, off, nq, qoff, sampled=True):
         else:
             paths.append("sampled" if sampled and qt >= SAMPLED_PAY else "direct")
     return paths
+
+
+def tile_walk(n, off, nq, qoff, cus, sampled=True):
+    """Per workgroup of search_kernel, the (path, segment) of each of its tiles in the order it walks them: ('resident' | 'sampled', the
+    segment it stages), ('direct', None), or (None, None) for a tile without a live query.  A workgroup keeps what it staged while path
+    and segment stay the same and restages when either changes, so the ordered pairs inside a workgroup say what it does."""
+    segs = segments(n, off, nq, qoff)
+    starts = np.array([c for _, _, c, _ in segs] + [segs[-1][3]], dtype=np.int64)
+    paths = tile_paths(n, off, nq, qoff, sampled)
+    chunk = max(-(-len(paths) // (16 * cus)), 1)
+    walk = []
+    for t, p in enumerate(paths):
+        a = max(t * TILE_Q, int(starts[0]))
+        # the segment of the tile's first live query: the last one that starts at or before it (empty segments skipped)
+        seg = int(np.searchsorted(starts[:-1], a, side="right")) - 1 if p in ("resident", "sampled") else None
+        if t % chunk == 0:
+            walk.append([])
+        walk[-1].append((p, seg))
+    return walk
+
+
+def pairs_of(walk):
+    """the ordered pairs (tile, next tile) that occur inside a workgroup"""
+    return {(g[i], g[i + 1]) for g in walk for i in range(len(g) - 1)}
+
+
+# -- layouts with a little more than 1024 x 16 x CUs queries: a workgroup walks two tiles (tests/test_gpu_search_paths.py) --------------------
+
+CYCLE = [0, 7, 3000, 4097, 4096, 20000, 2000]       # haystack lengths of the even layouts: an odd count, so that it drifts against the tiles
+RAGGED_CYCLE = [3001, 4095, 1021, 3, 2000, 4090, 1, 2, 6, 0, 4093, 5000, 777]
+
+
+def even_layout(cus, Q):
+    """(n, off, nq): the even form, Q queries a segment, ceil((1024 x 16 x CUs + 1) / Q) segments with the lengths of CYCLE.  Q = 1536:
+    tiles are (inside segment 2k, across 2k and 2k + 1, inside 2k + 1) while workgroups pair them by two; Q = 2048: a workgroup's two tiles
+    lie inside one segment"""
+    S = -(-(TILE_Q * 16 * cus + 1) // Q)
+    off = np.concatenate([[0], np.cumsum([CYCLE[s % len(CYCLE)] for s in range(S)])]).astype(np.uint64)
+    return int(off[-1]), off, S * Q
+
+
+def one_segment_layout(cus, L):
+    """(n, None, nq): one segment of L keys, 1024 x 16 x CUs + 5 queries"""
+    return L, None, TILE_Q * 16 * cus + 5
+
+
+def ragged_dead_layout(cus):
+    """(n, off, nq, qoff): ragged queries.  qoff[0] = 3 x 1024 + 100: workgroup 0 is dead, workgroup 1 = (dead, live).  Then one whole
+    tile of queries per segment with the lengths of RAGGED_CYCLE, the haystack starting at 1: every workgroup restages in its second
+    tile, at starts of every residue mod 4.  qoff[S] lies in the first tile of a workgroup: (live, dead); the last workgroup is dead"""
+    tiles = 16 * cus + 2
+    whole = tiles - 4 - 4                                        # tiles 4 .. tiles - 5, one segment each
+    lengths = [3001] + [RAGGED_CYCLE[(s + 1) % len(RAGGED_CYCLE)] for s in range(whole)] + [1000]
+    off = np.concatenate([[1], 1 + np.cumsum(lengths)]).astype(np.uint64)
+    qcounts = [TILE_Q - 100] + [TILE_Q] * whole + [500]
+    qoff = np.concatenate([[3 * TILE_Q + 100], 3 * TILE_Q + 100 + np.cumsum(qcounts)]).astype(np.uint64)
+    return int(off[-1]) + 3, off, (tiles - 1) * TILE_Q + 5, qoff
 
 
 def sort_engine_order(x: np.ndarray, descending: bool = False) -> np.ndarray:

@@ -1,6 +1,7 @@
 """CPU checks of the stream compaction: header, exports, binding and the Python callables agree on rsx_segmented_compact; the two forms
 of the host referee (tests/_compact_ref.py) agree with each other and with a hand-made case; the layouts the GPU tests run reach the
-paths they are named after; and the call and the torch helpers fail loudly instead of working on the CPU."""
+paths they are named after; the tiled mirror of the kernels' arithmetic equals the referee, and its named faults show what walk_layout
+notices that the older layouts do not; and the call and the torch helpers fail loudly instead of working on the CPU."""
 import ctypes as C
 import itertools
 import os
@@ -185,6 +186,124 @@ def test_gpu_layouts_reach_their_paths():
     # nothing in range
     n, off = R.nothing_layout()
     assert set(tile_facts(n, off)[0]) == {"dead"}
+
+
+def test_walk_layout_reaches_what_a_workgroup_carries():
+    """the nine properties of walk_layout at 256 CUs, from the layout alone: grid, tile_facts and the tiles of every workgroup"""
+    T = R.TILE
+    n, off = R.walk_layout(256)
+    o = off.astype(np.int64)
+    S = o.size - 1
+    assert n == R.BIG_N and grid(n)[:3] == (4098, 4112, 2) and S == 1322 and np.all(np.diff(o) >= 0) and o[-1] < n
+    spans, _ = tile_facts(n, off)
+    groups = R.workgroups(n, 256)
+    assert len(groups) == 2049 and all(len(g) == 2 for g in groups) and groups[5] == [10, 11]
+    live = lambda t: spans[t] != "dead"
+    per_tile = np.bincount(o // T, minlength=len(spans) + 1)                     # offsets inside every tile
+    last_seg = lambda t: int(np.searchsorted(o, min((t + 1) * T, o[-1]) - 1, side="right")) - 1       # the segment of the tile's last live element
+    seen = {}                                                                     # property -> the first workgroup that shows it
+    for w, (t0, t1) in enumerate(groups):
+        # 1. (dead, live inside one segment whose front is dead: off[0] in its middle)
+        if not live(t0) and spans[t1] == 1 and o[0] // T == t1 and o[0] % T != 0:
+            seen.setdefault(1, w)
+        # 2. (live, dead): off[S] in the middle of the first tile
+        if live(t0) and not live(t1) and o[-1] // T == t0 and o[-1] % T != 0:
+            seen.setdefault(2, w)
+        # 4. at least 600 offsets of short segments in the first tile: the second tile's gallop starts beyond 600
+        if live(t0) and live(t1) and per_tile[t0] >= 600 and last_seg(t0) + 1 > 600:
+            first = int(np.searchsorted(o, t0 * T, side="left"))
+            assert np.diff(o[first:first + 601]).tolist() == R.burst(600)
+            seen.setdefault(4, w)
+        # 5. at least 300 empty segments exactly at the start of the second tile, behind a segment that ends there
+        at = np.flatnonzero(o == t1 * T)
+        if at.size >= 301 and o[at[0] - 1] < t1 * T and live(t0) and live(t1):
+            seen.setdefault(5, w)
+        # 6. more than 256 offsets inside the second tile
+        if per_tile[t1] > 256:
+            seen.setdefault(6, w)
+        # 7. (spans segments, inside one) and the reverse
+        if live(t0) and live(t1) and spans[t0] > 1 and spans[t1] == 1:
+            seen.setdefault("7a", w)
+        if live(t0) and live(t1) and spans[t0] == 1 and spans[t1] > 1:
+            seen.setdefault("7b", w)
+    assert seen == {1: 1, 2: 2047, 4: 2, 5: 2, 6: 2, "7a": 3, "7b": 4}, seen
+    # 3. the workgroup before the first live one and the one after the last live one exist and are wholly dead
+    alive = [w for w, g in enumerate(groups) if any(live(t) for t in g)]
+    assert alive == list(range(1, 2048)) and not any(live(t) for t in groups[0] + groups[2048])
+    # 8. one segment covers at least three whole workgroups; 9. the issue's lengths once behind it
+    d = np.diff(o)
+    long = int(np.argmax(d))
+    assert o[long + 1] // (2 * T) - -(-o[long] // (2 * T)) >= 3 and d[long] > 4000 * T
+    assert d[long + 1:long + 1 + len(R.LENGTHS)].tolist() == R.LENGTHS and long + 1 + len(R.LENGTHS) == S - 1
+    # and on another device: the same walk of two tiles
+    n2, off2 = R.walk_layout(304)
+    assert grid(n2, 304)[2] == 2 and len(off2) == len(off) and int(off2[-1]) < n2
+
+
+def _bits_equal(a, b):
+    return all(np.array_equal(x.view(np.uint8), y.view(np.uint8)) for x, y in zip(a, b))
+
+
+_CASES = {}
+
+
+def layout_case(name):
+    """(keys, off, mask, bounds) of a layout of _compact_ref, narrow uint32 keys (ties with the bounds); drawn once"""
+    if name not in _CASES:
+        rng = np.random.default_rng(sorted(["ragged", "big", "empties", "mid_tile", "nothing", "walk"]).index(name))
+        n, off = getattr(R, name + "_layout")()
+        keys = random_keys(np.uint32, n, rng, narrow=True)
+        mask = R.MASK_BYTES[rng.integers(0, R.MASK_BYTES.size, n)]
+        bounds = random_keys(np.uint32, len(off) - 1, rng, narrow=True)
+        _CASES[name] = keys, off, mask, bounds
+    return _CASES[name]
+
+
+_REFS = {}
+
+
+def mask_partition_ref(name):
+    """compact_oracle of the layout's mask form in partition mode (computed once: 2 s at 2^24 elements)"""
+    if name not in _REFS:
+        keys, off, mask, _ = layout_case(name)
+        _REFS[name] = compact_oracle(keys, off, mask=mask, partition=True)
+    return _REFS[name]
+
+
+@pytest.mark.parametrize("name", ["ragged", "empties", "mid_tile", "nothing", "big", "walk"])
+def test_tiled_mirror_equals_the_referee(name):
+    """compact_tiled without a fault is compact_oracle on every layout: every flag combination on the small ones, one call per kernel
+    path (staged compact, staged and per-element partition; mask and bound) on the two of 2^24 elements"""
+    keys, off, mask, bounds = layout_case(name)
+    if name in ("big", "walk"):
+        forms = [(dict(mask=mask), dict(partition=True)), (dict(bounds=bounds), dict(strict=True, invert=True))]
+    else:
+        forms = [(dict(mask=mask), kw) for kw in flag_combinations(False)] + [(dict(bounds=bounds), kw) for kw in flag_combinations(True)]
+    for args, kw in forms:
+        ref = mask_partition_ref(name) if "mask" in args and kw == dict(partition=True) else compact_oracle(keys, off, **args, **kw)
+        assert _bits_equal(R.compact_tiled(keys, off, **args, **kw), ref), (sorted(args), kw)
+    if name == "ragged":                                                           # descending, 8-byte keys, one segment, another device
+        k64 = keys.astype(np.float64) - 20.0
+        b64 = bounds.astype(np.float64) - 20.0
+        assert _bits_equal(R.compact_tiled(k64, off, bounds=b64, descending=True, partition=True, cus=3), compact_oracle(k64, off, bounds=b64, descending=True, partition=True))
+        assert _bits_equal(R.compact_tiled(keys, None, mask=mask, cus=1), compact_oracle(keys, None, mask=mask))
+
+
+# the layouts that test_gpu_compact.py had before walk_layout, and which of them each fault of compact_tiled leaves unchanged: on the
+# three small ones no workgroup walks a second tile and no offset lies on a tile's start; on `big` workgroup 0 starts tile 1 inside the
+# segment tile 0 ended in, and stages twice, but its offsets are 0, 4096 + 1000 and n - 3: none on a tile's start behind a live tile
+UNCHANGED = {"gallop": ["ragged", "empties", "mid_tile"], "boundary": ["ragged", "big", "empties", "mid_tile"], "stale_stage": ["ragged", "empties", "mid_tile"]}
+
+
+@pytest.mark.parametrize("fault", R.FAULTS)
+def test_walk_layout_sees_what_the_older_layouts_cannot(fault):
+    """each named fault of compact_tiled changes the result on walk_layout (mask form, partition, keys and index)"""
+    changed = {}
+    for name in ["ragged", "big", "empties", "mid_tile", "walk"]:
+        keys, off, mask, _ = layout_case(name)
+        changed[name] = not _bits_equal(R.compact_tiled(keys, off, mask=mask, partition=True, fault=fault), mask_partition_ref(name))
+    assert changed["walk"], f"walk_layout does not notice the fault {fault!r}"
+    assert [name for name in ["ragged", "big", "empties", "mid_tile"] if not changed[name]] == UNCHANGED[fault]
 
 
 def test_no_cpu_path(rsx):

@@ -1,5 +1,6 @@
 """CPU checks of the search in sorted segments: header, exports, binding and the Python callables agree on rsx_segmented_search; the two
-forms of the host referee (tests/_search_ref.py) agree with each other and with a hand-made case; and the call and the torch helpers fail
+forms of the host referee (tests/_search_ref.py) agree with each other and with a hand-made case; the layouts whose workgroups walk two
+tiles of queries hold the (path, segment) transitions they are named for; and the call and the torch helpers fail
 loudly instead of working on the CPU."""
 import ctypes as C
 import re
@@ -182,6 +183,64 @@ def test_tile_paths_of_the_referee():
     off = np.array([0, 4096, 8192], dtype=np.uint64)
     assert R.tile_paths(8192, off, 2048, None) == ["resident", "resident"] and R.tile_paths(8192, off, 32, None) == ["direct"]
     assert R.tile_paths(8192, off, 3000, np.array([1024, 2000, 2400], dtype=np.uint64)) == [None, "direct", "resident"]
+
+
+def test_tile_walk_of_the_referee():
+    """per workgroup the (path, staged segment) of its tiles, on a device of one CU: 16 workgroups, two or three tiles each"""
+    walk = R.tile_walk(4000, None, 17 * 1024 + 5, None, cus=1)                    # 18 tiles: nine workgroups of two
+    assert walk == [[("resident", 0), ("resident", 0)]] * 8 + [[("resident", 0), ("direct", None)]]
+    off = np.array([0, 4096, 8192, 8192 + 5000], dtype=np.uint64)
+    qoff = np.array([1024, 2000, 3072, 33 * 1024 - 7], dtype=np.uint64)
+    walk = R.tile_walk(8192 + 5000, off, 33 * 1024, qoff, cus=1)                  # 33 tiles: eleven workgroups of three
+    assert len(walk) == 11 and walk[0] == [(None, None), ("direct", None), ("resident", 1)] and walk[1] == [("sampled", 2)] * 3
+    assert R.tile_walk(8192 + 5000, off, 33 * 1024, qoff, cus=1, sampled=False)[10] == [("direct", None)] * 3
+    assert R.tile_walk(8192 + 5000, off, 33 * 1024, qoff, cus=3)[0] == [(None, None)] and R.tile_walk(8192, off[:3], 2048, None, cus=1) == [[("resident", 0)], [("resident", 1)]]
+    assert R.pairs_of(walk) >= {((None, None), ("direct", None)), (("direct", None), ("resident", 1)), (("sampled", 2), ("sampled", 2))}
+
+
+def kinds_of(walk):
+    """the ordered pairs inside a workgroup as (path, path, 'same' | 'other' staged segment | None where one of the two stages nothing)"""
+    return {(a[0], b[0], None if a[1] is None or b[1] is None else "same" if a[1] == b[1] else "other") for a, b in R.pairs_of(walk)}
+
+
+def test_two_tile_layouts_reach_their_transitions():
+    """the layouts of tests/test_gpu_search_paths.py at 256 CUs: every workgroup walks two tiles, and the ordered pairs of (path, segment)
+    that each layout is there for occur inside one workgroup"""
+    cus = 256
+    two = lambda walk: len(walk) == 2049 and all(len(g) == 2 for g in walk[:-1]) and 1 <= len(walk[-1]) <= 2
+    n, off, nq = R.even_layout(cus, 1536)
+    assert n == 12948000 and nq == 2731 * 1536 and nq % (len(off) - 1) == 0
+    walk = R.tile_walk(n, off, nq, None, cus)
+    assert two(walk) and kinds_of(walk) >= {("resident", "resident", "other"), ("resident", "sampled", "other"), ("sampled", "resident", "other"),
+                                            ("resident", "direct", None), ("direct", "resident", None), ("sampled", "direct", None),
+                                            ("direct", "sampled", None)}
+    plain = R.tile_walk(n, off, nq, None, cus, sampled=False)                     # RSX_SEARCH_SAMPLED=0: the sampled tiles take the direct path
+    assert [[(p if p != "sampled" else "direct", s if p == "resident" else None) for p, s in g] for g in walk] == plain
+    assert ("direct", "direct", None) in kinds_of(plain) and not any(p == "sampled" for g in plain for p, _ in g)
+    n, off, nq = R.even_layout(cus, 2048)
+    walk = R.tile_walk(n, off, nq, None, cus)
+    assert two(walk) and kinds_of(walk) == {("resident", "resident", "same"), ("sampled", "sampled", "same")}
+    for L, path in ((4000, "resident"), (50000, "sampled")):
+        n, off, nq = R.one_segment_layout(cus, L)
+        walk = R.tile_walk(n, off, nq, None, cus)
+        assert two(walk) and walk[:-1] == [[(path, 0), (path, 0)]] * 2048 and walk[-1] == [("direct", None)]
+    n, off, nq, qoff = R.ragged_dead_layout(cus)
+    walk = R.tile_walk(n, off, nq, qoff, cus)
+    S = len(off) - 1
+    assert two(walk) and int(qoff[-1]) < nq and int(off[-1]) < n and len(qoff) == len(off)
+    assert walk[0] == [(None, None), (None, None)] and walk[1] == [(None, None), ("resident", 0)]          # dead tiles at the head,
+    assert walk[-2] == [("resident", S - 1), (None, None)] and walk[-1] == [(None, None), (None, None)]    # and at the tail
+    assert (int(qoff[-1]) // R.TILE_Q) % 2 == 0 and int(qoff[-1]) % R.TILE_Q != 0
+    assert {int(o) % 4 for o in off[:-1]} == {0, 1, 2, 3}
+    assert kinds_of(walk) >= {("resident", "resident", "other"), ("resident", "sampled", "other"), ("sampled", "resident", "other")}
+    o = off.astype(np.int64)
+    both = 0                                                                     # second tiles that restage a segment with a head and a tail around its 16-byte vectors
+    for g in walk:
+        if len(g) == 2 and g[1][0] == "resident" and g[0][1] != g[1][1]:
+            hs, L = o[g[1][1]], o[g[1][1] + 1] - o[g[1][1]]
+            head = min((4 - hs % 4) % 4, L)
+            both += int(head > 0 and (L - head) % 4 > 0 and L - head >= 4)
+    assert both >= 100
 
 
 def test_no_cpu_path(rsx):
