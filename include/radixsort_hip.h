@@ -538,6 +538,44 @@ int rsx_segmented_search(rsx_engine* e, const void* d_sorted, uint64_t n, const 
 int rsx_segmented_compact(rsx_engine* e, const void* d_keys, uint64_t n, const uint64_t* d_offsets /* or NULL */, uint64_t num_segments,
                           const uint8_t* d_mask /* or NULL */, const void* d_bounds /* or NULL */, uint32_t flags,
                           void* d_keys_out /* or NULL */, uint32_t* d_index_out /* or NULL */, uint64_t* d_kept_offsets_out);
+/* rsx_segmented_merge: the stable merge of sorted segment s of A with sorted segment s of B, for every s, in one pass over the keys
+ *   (std::merge, thrust::merge / merge_by_key, cub::DeviceMerge, with ragged rows).  Nothing is sorted: every key is read once and
+ *   written once.
+ *   SEGMENTS.  Segment s of A is d_a[aoff[s] .. aoff[s+1]), La keys; segment s of B is d_b[boff[s] .. boff[s+1]), Lb keys; both are sorted
+ *   in the ENGINE's order: its key kind (floats: IEEE 754 totalOrder) and direction (RSX_OPT_DESCENDING), i.e. what rsx_segmented_sort or
+ *   rsx_sort_from of an engine of the same kind and direction leaves.  Both offsets arrays NULL: one segment [0, na) and [0, nb); one
+ *   NULL and one given is refused.  Keys have the engine's key type; the payloads are one 32-bit word per key.
+ *   RESULT.  ooff[s] = (aoff[s] - aoff[0]) + (boff[s] - boff[0]): the packing is dense from 0, as rsx_segmented_unique's and
+ *   rsx_segmented_compact's, and ooff[S] is the total.  d_out_offsets, when non-NULL, gets these S + 1 uint64.  Output segment
+ *   [ooff[s], ooff[s+1]) holds the STABLE SORT in the engine's order OF THE CONCATENATION A_s ++ B_s; for sorted inputs that is the stable
+ *   merge: keys that are equal by bits keep the order within their side, and every A element comes before the B elements equal to it.  Key
+ *   bits are unchanged; -0.0 sorts before +0.0 and a NaN is an ordinary key.  d_index_out[ooff[s] + r] = j is the position in that
+ *   concatenation: j < La means A_s[j], otherwise B_s[j - La]: exactly what a stable argsort of the concatenation holds at r.
+ *   d_payload_out gets the payload word that came with each key; the two payload inputs and d_payload_out are all given or all NULL.
+ *   d_keys_out, d_index_out and d_out_offsets may each be NULL; with no output asked for at all the call is refused.  Nothing at or past
+ *   ooff[S] is written.
+ *   INPUTS THAT ARE NOT SORTED give an unspecified order; every access stays inside the buffers and exactly [0, ooff[S]) is written.
+ *   HOW.  Tiles of 4096 OUTPUT positions.  One thread per tile boundary finds its segment and merge-path split (a bisection over the
+ *   segments, one over the diagonal; A before equal B) and the output offsets are written; then a workgroup per tile (several tiles above
+ *   16 x CUs tiles) stages the tile's sources - one contiguous range of A and one of B, 4096 keys together - in LDS, every thread merges 16
+ *   consecutive outputs there, and the tile leaves as consecutive addresses (rsx_merge.hpp).  No atomics: the output is a function of the
+ *   inputs alone.  Bytes: (na + nb) (2 key [+ 8 with payload] [+ 4 with index]) plus 8 per tile.
+ *   THE ENGINE'S SORT STATE IS UNTOUCHED, whatever the engine's has_payload: na + nb may exceed the capacity and an earlier sort's result
+ *   stays valid; only the per-tile splits grow, outside stream captures.  Asynchronous on the engine's stream, nothing read back, every
+ *   launch sized from na, nb and num_segments: capturable.  Offsets are validated on the device, aoff against na and boff against nb:
+ *   with off[s+1] < off[s] or off[s+1] > n in either, every kernel leaves at once, d_out_offsets is all zeros, nothing else is written,
+ *   and the next rsx_sync / rsx_check_status reports RSX_CALCULATION_FAILED once, naming this call and the first such segment; the
+ *   engine stays usable.
+ *   REFUSED AT ONCE: RSX_CALCULATION_FAILED for a null engine, flags != 0 (no bit is defined; the argument exists because an ABI cannot
+ *   grow one later), one offsets array without the other, na, nb or na + nb above 2^31, 2^32 - 1 segments or more, no output requested,
+ *   payload pointers not all given or all NULL; RSX_HOST_BUFFERS_FAILED for a null d_a with na > 0 or a null d_b with nb > 0, a d_a or d_b
+ *   that is not 16-byte aligned, payloads or outputs not aligned to their element, offsets not 8-byte aligned, any overlap of an output
+ *   with an input or another output (there is no in-place form), anything overlapping the engine's buffers.  na + nb == 0 (or
+ *   num_segments == 0 with offsets) launches and writes nothing; one empty side is valid: the result is a copy of the other side. */
+int rsx_segmented_merge(rsx_engine* e, const void* d_a, const uint32_t* d_a_payload /* or NULL */, uint64_t na, const uint64_t* d_a_offsets /* or NULL */,
+                        const void* d_b, const uint32_t* d_b_payload /* or NULL */, uint64_t nb, const uint64_t* d_b_offsets /* or NULL */,
+                        uint64_t num_segments, uint32_t flags /* must be 0 */, void* d_keys_out /* or NULL */, uint32_t* d_payload_out /* or NULL */,
+                        uint32_t* d_index_out /* or NULL */, uint64_t* d_out_offsets /* or NULL */);
 /* Receive buffers other ranks can write to (the peer-store exchange below): rsx_peer_alloc (hipMalloc + an IPC handle to hand to the other
  * PROCESSES, which map it with rsx_peer_open / rsx_peer_close — peer access over xGMI); ranks that are threads of one process use the
  * pointer itself (after rsx_peer_enable, once per other device). */

@@ -52,7 +52,7 @@ SYMBOLS = [
     "rsx_create", "rsx_destroy", "rsx_set_stream", "rsx_get_stream", "rsx_set_option", "rsx_get_geometry", "rsx_resize",
     "rsx_upload", "rsx_fill_pad", "rsx_download", "rsx_pin_host", "rsx_unpin_host", "rsx_pipeline_submit", "rsx_pipeline_wait", "rsx_host_device_pointer",
     "rsx_histogram", "rsx_scan", "rsx_paste", "rsx_reorder", "rsx_sort", "rsx_sync", "rsx_check_status",
-    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
+    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_segmented_merge", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
 ]
 
 
@@ -165,6 +165,7 @@ def load_library() -> C.CDLL:
         "rsx_segmented_scan": ([P, P, P, U64, P, U64, C.c_uint32, C.c_uint32, C.c_uint32, P], I),
         "rsx_segmented_search": ([P, P, U64, P, U64, P, U64, P, C.c_uint32, P], I),
         "rsx_segmented_compact": ([P, P, U64, P, U64, P, P, C.c_uint32, P, P, P], I),
+        "rsx_segmented_merge": ([P, P, P, U64, P, P, P, U64, P, U64, C.c_uint32, P, P, P, P], I),
         "rsx_msd_count": ([P, P, U64, I, I, P], I),
         "rsx_msd_scatter": ([P, P, P, U64, P, P], I),
         "rsx_msd_plan": ([P, P, C.c_uint32, C.c_uint32, I, I, P], I),
@@ -539,6 +540,22 @@ class Engine:
         self._check(self.lib.rsx_segmented_compact(
             self._h, opt(d_keys), n, opt(d_offsets), num_segments, opt(d_mask), opt(d_bounds), flags, opt(d_keys_out), opt(d_index_out),
             opt(d_kept_offsets_out)), "rsx_segmented_compact")
+
+    def segmented_merge(self, d_a: int | None, na: int, d_a_offsets: int | None, d_b: int | None, nb: int, d_b_offsets: int | None, num_segments: int,
+                        d_keys_out: int | None, d_index_out: int | None = None, d_out_offsets: int | None = None, d_a_payload: int | None = None,
+                        d_b_payload: int | None = None, d_payload_out: int | None = None, flags: int = 0) -> None:
+        """The stable merge of sorted segment s of A, d_a[aoff[s] .. aoff[s+1]), with sorted segment s of B, for every s, in one pass: output
+        segment [ooff[s], ooff[s+1]), ooff[s] = (aoff[s] - aoff[0]) + (boff[s] - boff[0]), holds the stable sort in the engine's order of
+        A_s ++ B_s (an A key before the B keys equal to it), d_index_out (uint32) the position of every output in that concatenation,
+        d_payload_out the 32-bit payload word that came with each key (the three payload pointers all or none), d_out_offsets
+        (num_segments + 1 uint64) the ooff.  Both offsets None: ONE segment [0, na) and [0, nb).  The segments must be sorted in the
+        engine's order (key kind, totalOrder for floats, direction).  Each output may be None, not all.  na + nb may exceed the capacity,
+        the engine's sort result is left alone, and has_payload does not matter.  Asynchronous on the engine's stream; bad offsets
+        (d_out_offsets holds zeros then, nothing else is written) are reported by the next sync() / check_status()."""
+        opt = lambda p: C.c_void_p(p) if p else None
+        self._check(self.lib.rsx_segmented_merge(
+            self._h, opt(d_a), opt(d_a_payload), na, opt(d_a_offsets), opt(d_b), opt(d_b_payload), nb, opt(d_b_offsets), num_segments, flags,
+            opt(d_keys_out), opt(d_payload_out), opt(d_index_out), opt(d_out_offsets)), "rsx_segmented_merge")
 
     # -- exchange step of the sharded sort on the top B <= 8 bits ----------------
     def msd_count(self, d_keys: int, n: int, bits: int, world: int, d_counts: int) -> None:
@@ -1559,3 +1576,104 @@ def compact_rows(x, mask=None, bound=None, strict: bool = False, invert: bool = 
         b = bound.expand(x.shape[:-1]).contiguous().reshape(-1)
     v, ko, idx = _compact_call("compact_rows", flat, offsets, m, b, strict, invert, descending, False, True, return_index)
     return (v, ko) + ((idx,) if return_index else ())
+
+
+# -- merge on torch tensors -------------------------------------------------------------------------------------------------------------
+def _merge_call(what: str, a, a_offsets, b, b_offsets, payload_a, payload_b, descending: bool, want_index: bool):
+    """One rsx_segmented_merge call on 1-D device tensors (both offsets None: one segment).  Returns (keys, out_offsets, payload, index):
+    keys, payload and index have na + nb entries, zero (index: -1) from out_offsets[-1] on; nothing is read back."""
+    import torch
+    for name, t in (("a", a), ("b", b)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{what}: {name} must be a tensor")
+    name = str(a.dtype).replace("torch.", "")
+    if name not in _KEY_DTYPES:
+        raise TypeError(f"{what}: unsupported key type {a.dtype}")
+    if b.dtype != a.dtype:
+        raise TypeError(f"{what}: a is {a.dtype}, b {b.dtype} (convert one of them: the merge compares keys of one type)")
+    if not a.is_cuda or not b.is_cuda:
+        raise ValueError(f"{what}: a and b must be device tensors (there is no CPU path)")
+    if a.dim() != 1 or b.dim() != 1 or b.device != a.device:
+        raise ValueError(f"{what}: a and b must be 1-D tensors on one device")
+    if (a_offsets is None) != (b_offsets is None):
+        raise ValueError(f"{what}: a_offsets and b_offsets must both be given or both be None")
+    for oname, o in (("a_offsets", a_offsets), ("b_offsets", b_offsets)):
+        if o is not None and (not torch.is_tensor(o) or o.dtype != torch.int64 or o.dim() != 1 or o.device != a.device):
+            raise ValueError(f"{what}: {oname} must be a 1-D int64 tensor on the keys' device")
+    if a_offsets is not None and a_offsets.numel() != b_offsets.numel():
+        raise ValueError(f"{what}: a_offsets and b_offsets must have the same number of entries")
+    if (payload_a is None) != (payload_b is None):
+        raise ValueError(f"{what}: payload_a and payload_b must both be given or both be None")
+    u32 = getattr(torch, "uint32", torch.int32)
+    for pname, p, k in (("payload_a", payload_a, a), ("payload_b", payload_b, b)):
+        if p is not None and (not torch.is_tensor(p) or p.shape != k.shape or p.device != k.device or p.dtype not in (torch.int32, u32)):
+            raise ValueError(f"{what}: {pname} must be an int32 / uint32 tensor shaped like its keys, on the same device")
+    if payload_a is not None and payload_a.dtype != payload_b.dtype:
+        raise ValueError(f"{what}: payload_a and payload_b must have one dtype")
+    na, nb = a.numel(), b.numel()
+    if na + nb > (1 << 31):
+        raise ValueError(f"{what}: at most 2^31 keys together (rsx_segmented_merge's bound)")
+    nseg = 1 if a_offsets is None else max(a_offsets.numel() - 1, 0)
+    dev = a.device
+    keys = torch.zeros(na + nb, dtype=a.dtype, device=dev)
+    ooff = torch.zeros(nseg + 1, dtype=torch.int64, device=dev)
+    pay = None if payload_a is None else torch.zeros(na + nb, dtype=payload_a.dtype, device=dev)
+    index = torch.full((na + nb,), -1, dtype=torch.int32, device=dev) if want_index else None
+    if na + nb > 0 and nseg > 0:
+        a_in, b_in = _aligned_copy(a, torch), _aligned_copy(b, torch)
+        cont = lambda t: None if t is None else t if t.is_contiguous() and t.data_ptr() % 8 == 0 else t.clone(memory_format=torch.contiguous_format)
+        ao, bo, pa, pb = cont(a_offsets), cont(b_offsets), cont(payload_a), cont(payload_b)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        device = dev.index if dev.index is not None else torch.cuda.current_device()
+        eng = _search_engine(device, torch.cuda.current_stream(dev).cuda_stream, name, bool(descending))
+        if pay is not None:             # (an empty side has no storage: any aligned address stands in for its payload, which is not read)
+            pa_ptr, pb_ptr = (pa.data_ptr() if na else pay.data_ptr() + 4 * (na + nb)), (pb.data_ptr() if nb else pay.data_ptr() + 4 * (na + nb))
+        else:
+            pa_ptr = pb_ptr = None
+        eng.segmented_merge(ptr(a_in), na, ptr(ao), ptr(b_in), nb, ptr(bo), nseg, keys.data_ptr(), ptr(index), ooff.data_ptr(),
+                            d_a_payload=pa_ptr, d_b_payload=pb_ptr, d_payload_out=ptr(pay))
+        eng.check_status()      # reports bad offsets of calls that have already finished; no synchronisation
+    return keys, ooff, pay, (None if index is None else index.to(torch.int64))
+
+
+def segmented_merge(a, a_offsets, b, b_offsets, payload_a=None, payload_b=None, descending: bool = False, return_index: bool = False):
+    """The stable merge of sorted segment a[a_offsets[s] : a_offsets[s+1]] with sorted segment b[b_offsets[s] : b_offsets[s+1]], for every
+    s, in ONE engine call (rsx_segmented_merge) that reads every key once: returns (keys, out_offsets[, payload][, index]).  a and b are
+    1-D device tensors of one dtype, the offsets int64 (both None: one segment each).  out_offsets[s] = (a_offsets[s] - a_offsets[0]) +
+    (b_offsets[s] - b_offsets[0]); keys[out_offsets[s] : out_offsets[s+1]] is the stable sort of the concatenation of the two segments in
+    this library's order: equal keys keep the order of their side and those of a come before those of b.  The segments must be sorted as
+    this library sorts them (segmented_sort / sort_rows with the same `descending`): floats in IEEE 754 totalOrder, -0.0 before +0.0, NaN an
+    ordinary largest or smallest key; inputs that are not sorted give an unspecified order.  payload_a / payload_b (int32 / uint32, both
+    or neither): the word that came with each key.  index (int64): the position of every output in the concatenation of its two segments
+    (below the a segment's length: from a).  The outputs have a.numel() + b.numel() entries and are zero (index: -1) from out_offsets[-1]
+    on.  Never synchronises with the host; bad offsets raise RadixSortError at a later call or synchronisation of the engine."""
+    k, oo, p, idx = _merge_call("segmented_merge", a, a_offsets, b, b_offsets, payload_a, payload_b, descending, return_index)
+    return (k, oo) + ((p,) if p is not None else ()) + ((idx,) if return_index else ())
+
+
+def merge(a, b, payload_a=None, payload_b=None, descending: bool = False, return_index: bool = False):
+    """The stable merge of two sorted device tensors along their last dimension: 1-D inputs are one segment; N-D inputs with equal leading
+    shape are merged row by row, the rows being the segments of ONE rsx_segmented_merge call.  Returns keys of shape [..., La + Lb]
+    (with payloads: (keys, payload); with return_index=True the int64 positions in torch.cat([a, b], -1) of every output last).  Equal to
+    torch.sort(torch.cat([a, b], -1), dim=-1, stable=True, descending=descending) for rows sorted in this library's order (integer dtypes,
+    and floats without -0.0 and NaN, equal torch exactly).  Order, payloads and errors as segmented_merge."""
+    import torch
+    for name, t in (("a", a), ("b", b)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"merge: {name} must be a tensor")
+    if a.dim() == 0 or a.dim() != b.dim() or tuple(a.shape[:-1]) != tuple(b.shape[:-1]):
+        raise ValueError("merge: a and b must have the same number of dimensions (at least one) and equal leading shape")
+    for pname, p, k in (("payload_a", payload_a, a), ("payload_b", payload_b, b)):
+        if p is not None and (not torch.is_tensor(p) or p.shape != k.shape):
+            raise ValueError(f"merge: {pname} must be a tensor shaped like its keys")
+    la, lb = a.shape[-1], b.shape[-1]
+    flat = lambda t: None if t is None else t.contiguous().reshape(-1)
+    ao = bo = None
+    if a.dim() > 1:
+        rows = a.numel() // la if la else (b.numel() // lb if lb else 0)
+        steps = torch.arange(0, rows + 1, device=a.device, dtype=torch.int64)
+        ao, bo = steps * la, steps * lb
+    k, _, p, idx = _merge_call("merge", flat(a), ao, flat(b), bo, flat(payload_a), flat(payload_b), descending, return_index)
+    shape = tuple(a.shape[:-1]) + (la + lb,)
+    res = (k.reshape(shape),) + ((p.reshape(shape),) if p is not None else ()) + ((idx.reshape(shape),) if return_index else ())
+    return res[0] if len(res) == 1 else res

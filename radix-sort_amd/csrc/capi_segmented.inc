@@ -52,6 +52,7 @@ int ensure_segmented(rsx_engine* e, const SegShape& s, uint64_t nseg)
         RSX_TRY(hipMalloc(reinterpret_cast<void**>(&e->seg_temp), 64), RSX_INITIALIZATION_FAILED);
         RSX_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->seg_status_host), 64, hipHostMallocMapped), RSX_HOST_BUFFERS_FAILED);
         e->seg_status_host[0] = 0;
+        e->seg_status_host[1] = 0;       // (which call reported: capi_merge.inc)
         RSX_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->seg_status), e->seg_status_host, 0), RSX_HOST_BUFFERS_FAILED);
     }
     if (rc == RSX_OK) rc = seg_grow(e, &e->seg_bsum, &e->seg_bsum_cap, s.nblocks * rsx::SF_STRIDE, "the classify block sums");

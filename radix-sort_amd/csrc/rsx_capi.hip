@@ -20,6 +20,7 @@
 #include "rsx_scan_by_key.hpp"
 #include "rsx_search.hpp"
 #include "rsx_compact.hpp"
+#include "rsx_merge.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -229,6 +230,9 @@ struct rsx_engine {
     uint64_t red_part_cap = 0;
     // rsx_segmented_search (capi_search.inc): no scratch; which path a tile inside one long segment takes
     int search_sampled = 1;                     // 0: such tiles search global memory directly (env RSX_SEARCH_SAMPLED, for tools/search_bench.py)
+    // rsx_segmented_merge (capi_merge.inc): the segment and merge-path split of every tile boundary
+    rsx::MergeSplit* merge_split = nullptr;
+    uint64_t merge_split_cap = 0;
 
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -1245,6 +1249,7 @@ int sort_chain(rsx_engine* e, const SortJob& job)
 // (the flag is a word of mapped pinned host memory that the kernel stores to at system scope: reading it costs no copy and no
 // synchronisation, so it is also looked at by the asynchronous calls — there it reports a time-out of work that has already
 // finished; the synchronising calls look after their hipStreamSynchronize.)  Reported once, then cleared: the engine stays usable.
+constexpr uint32_t kStatusCallMerge = 1;         // word 1 of the mapped status words: written by the call that reports, beside its segment in word 0
 int check_scan_timeout(rsx_engine* e, int status)
 {
     if (e->seg_status_host) {
@@ -1252,7 +1257,13 @@ int check_scan_timeout(rsx_engine* e, int status)
         volatile uint32_t* bad = e->seg_status_host;
         const uint32_t v = *bad;
         if (v != 0) {
+            const uint32_t call = bad[1];       // word 1: which call reported (0: one of the calls that share the message below)
+            bad[1] = 0;
             *bad = 0;
+            if (call == kStatusCallMerge)
+                return fail(status, ("rsx_segmented_merge: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n in d_a_offsets (n = na) or in "
+                                     "d_b_offsets (n = nb); d_out_offsets holds zeros and nothing else was written (the first such segment of the call; "
+                                     "reported once; the engine remains usable)").c_str());
             return fail(status, ("rsx_segmented_sort / rsx_segmented_topk / rsx_segmented_select: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; it was neither read nor "
                                  "written (the first such segment of the call; reported once; the engine remains usable)").c_str());
         }
@@ -1628,7 +1639,7 @@ int rsx_destroy(rsx_engine* e)
     for (void* p : {static_cast<void*>(e->seg_hdr), static_cast<void*>(e->seg_temp), static_cast<void*>(e->seg_bsum), static_cast<void*>(e->seg_list),
                     static_cast<void*>(e->seg_large), static_cast<void*>(e->seg_tstart), static_cast<void*>(e->seg_table), static_cast<void*>(e->seg_gsum),
                     static_cast<void*>(e->seg_gsum2), static_cast<void*>(e->topk_state), static_cast<void*>(e->topk_start),
-                    static_cast<void*>(e->topk_cont), static_cast<void*>(e->uniq_iota), static_cast<void*>(e->red_part)}) {
+                    static_cast<void*>(e->topk_cont), static_cast<void*>(e->uniq_iota), static_cast<void*>(e->red_part), static_cast<void*>(e->merge_split)}) {
         if (p && hipFree(p) != hipSuccess) status = RSX_CLEANUP_FAILED;
     }
     if (e->seg_status_host && hipHostFree(e->seg_status_host) != hipSuccess) status = RSX_CLEANUP_FAILED;
@@ -2384,6 +2395,7 @@ int rsx_peer_enable(rsx_engine* e, int peer_device)
 #include "capi_scan.inc"
 #include "capi_search.inc"
 #include "capi_compact.inc"
+#include "capi_merge.inc"
 
 int rsx_key_range(rsx_engine* e, const void* d_keys, uint64_t n, uint64_t* lo, uint64_t* hi)
 {
