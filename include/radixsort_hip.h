@@ -576,6 +576,53 @@ int rsx_segmented_merge(rsx_engine* e, const void* d_a, const uint32_t* d_a_payl
                         const void* d_b, const uint32_t* d_b_payload /* or NULL */, uint64_t nb, const uint64_t* d_b_offsets /* or NULL */,
                         uint64_t num_segments, uint32_t flags /* must be 0 */, void* d_keys_out /* or NULL */, uint32_t* d_payload_out /* or NULL */,
                         uint32_t* d_index_out /* or NULL */, uint64_t* d_out_offsets /* or NULL */);
+/* rsx_segmented_set_op: intersection, difference, union or symmetric difference of sorted segment s of A with sorted segment s of B, for
+ *   every s, in two passes over the keys (std::set_intersection / set_difference / set_union / set_symmetric_difference with duplicates,
+ *   thrust::set_*_by_key, with ragged rows).  A set operation is the merge of rsx_segmented_merge whose outputs pass a predicate.
+ *   SEGMENTS, ORDER AND EQUALITY as rsx_segmented_merge: segment s of A is d_a[aoff[s] .. aoff[s+1]), of B d_b[boff[s] .. boff[s+1]), both
+ *   sorted in the ENGINE's order (key kind, IEEE 754 totalOrder for floats, direction); both offsets arrays NULL is the one segment
+ *   [0, na) and [0, nb).  Keys are equal iff their bits are (-0.0 and +0.0 differ, NaNs with equal bits are one key).
+ *   WHICH ELEMENTS ARE KEPT.  A key x occurs m times in A_s and n times in B_s; number its occurrences on each side r = 0, 1, ... in input
+ *   order.  RSX_SET_INTERSECTION keeps the A occurrences r < n (min(m, n), all from A); RSX_SET_DIFFERENCE the A occurrences r >= n (the
+ *   last max(m - n, 0) of A); RSX_SET_UNION every A occurrence and the B occurrences r >= m (max(m, n)); RSX_SET_SYMMETRIC_DIFFERENCE the
+ *   A occurrences r >= n and the B occurrences r >= m (|m - n|): what std::set_* keeps.
+ *   RESULT.  The kept elements of segment s appear in the order of the stable merge of A_s ++ B_s (A before equal B, each side in its own
+ *   order), packed densely across segments: d_out_offsets[s] = koff[s] = the number kept before segment s, koff[0] = 0, koff[S] the
+ *   total (S + 1 uint64; REQUIRED).  d_keys_out gets the keys (bits unchanged); d_payload_out the 32-bit word that came with each key (the
+ *   two payload inputs and d_payload_out are all given or all NULL); d_index_out the position in A_s ++ B_s, the merge's convention
+ *   (below La: A_s[j], otherwise B_s[j - La]); d_match_out (RSX_SET_INTERSECTION only) for the kept A occurrence r of x the position
+ *   relative to boff[s] of B's occurrence r of x: index and match together are an inner join.  Each of these four may be NULL; with all
+ *   NULL the call only counts.  Nothing at or past koff[S] is written in any output.  BUFFER SIZES: na elements for intersection and
+ *   difference, na + nb for union and symmetric difference; the overlap checks use these sizes.
+ *   INPUTS THAT ARE NOT SORTED give an unspecified result; every access stays inside the buffers, koff is non-decreasing, koff[S] is at
+ *   most the buffer size above and exactly [0, koff[S]) is written (both passes evaluate the predicate with one function on the same
+ *   data, and destinations are capped at the buffer size).
+ *   HOW.  The merge's grid: tiles of 4096 merged positions, a workgroup per tile (several above 16 x CUs tiles), the merge's split per
+ *   tile boundary.  A count pass stages the tile's A range and B range in LDS, merges, and asks per merged element with ONE probe of the
+ *   other side whether it has a partner there (rsx_setop.hpp); the per-tile counts are scanned; a write pass repeats the merge and the
+ *   predicate, ranks the kept elements and stores them as consecutive addresses.  No atomic decides a destination.  Bytes: 2 (na + nb)
+ *   key reads [+ 4 (na + nb) with payload] + kept x (key [+ 4 payload] [+ 4 index] [+ 4 match]), plus 12 per tile.
+ *   THE ENGINE'S SORT STATE IS UNTOUCHED, whatever the engine's has_payload: na + nb may exceed the capacity and an earlier sort's result
+ *   stays valid; only the per-tile splits and the per-tile table grow, outside stream captures.  Asynchronous on the engine's stream,
+ *   nothing read back, every launch sized from na, nb and num_segments: capturable.  Offsets are validated on the device as the merge's:
+ *   with a bad segment in either array d_out_offsets is all zeros, nothing else is written, and the next rsx_sync / rsx_check_status
+ *   reports RSX_CALCULATION_FAILED once, naming this call and the first such segment; the engine stays usable.
+ *   REFUSED AT ONCE: RSX_CALCULATION_FAILED for a null engine, op > 3, flags != 0, a d_match_out with an op other than
+ *   RSX_SET_INTERSECTION, one offsets array without the other, na, nb or na + nb above 2^31, 2^32 - 1 segments or more, payload pointers
+ *   not all given or all NULL; RSX_HOST_BUFFERS_FAILED for a null d_out_offsets, a null d_a with na > 0 or a null d_b with nb > 0, a d_a
+ *   or d_b that is not 16-byte aligned, payloads or outputs not aligned to their element, offsets not 8-byte aligned, any overlap of an
+ *   output with an input or another output, anything overlapping the engine's buffers.  na + nb == 0 (or num_segments == 0 with offsets)
+ *   launches and writes nothing.  With nb == 0 union, difference and symmetric difference give A back and intersection nothing but zero
+ *   offsets. */
+#define RSX_SET_INTERSECTION 0
+#define RSX_SET_DIFFERENCE 1             /* A minus B */
+#define RSX_SET_UNION 2
+#define RSX_SET_SYMMETRIC_DIFFERENCE 3
+int rsx_segmented_set_op(rsx_engine* e, const void* d_a, const uint32_t* d_a_payload /* or NULL */, uint64_t na, const uint64_t* d_a_offsets /* or NULL */,
+                         const void* d_b, const uint32_t* d_b_payload /* or NULL */, uint64_t nb, const uint64_t* d_b_offsets /* or NULL */,
+                         uint64_t num_segments, uint32_t op, uint32_t flags /* must be 0 */,
+                         void* d_keys_out /* or NULL */, uint32_t* d_payload_out /* or NULL */, uint32_t* d_index_out /* or NULL */,
+                         uint32_t* d_match_out /* or NULL; intersection only */, uint64_t* d_out_offsets);
 /* Receive buffers other ranks can write to (the peer-store exchange below): rsx_peer_alloc (hipMalloc + an IPC handle to hand to the other
  * PROCESSES, which map it with rsx_peer_open / rsx_peer_close — peer access over xGMI); ranks that are threads of one process use the
  * pointer itself (after rsx_peer_enable, once per other device). */

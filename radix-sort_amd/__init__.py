@@ -42,6 +42,7 @@ VALUE_INT32, VALUE_INT64, VALUE_FLOAT32, VALUE_FLOAT64 = 0, 1, 2, 3           # 
 SCAN_EXCLUSIVE = 2         # RSX_SCAN_EXCLUSIVE: flags bit 1 of rsx_segmented_scan
 SEARCH_RIGHT = 4           # RSX_SEARCH_RIGHT: flags bit 2 of rsx_segmented_search
 COMPACT_PARTITION, COMPACT_INVERT, COMPACT_STRICT = 8, 16, 32                  # RSX_COMPACT_*: flags bits 3, 4, 5 of rsx_segmented_compact
+SET_INTERSECTION, SET_DIFFERENCE, SET_UNION, SET_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3       # RSX_SET_*: op of rsx_segmented_set_op
 # rsx_experimental_option (include/radixsort_hip_experiments.h): known to the EXPERIMENTS build only (experiments()); the product library refuses them
 XOPT_DEBUG_RAISE_SCAN_TIMEOUT, XOPT_INLINE_SCAN, XOPT_INLINE_SCAN_MAX_GROUPS, XOPT_REORDER8_KERNEL, XOPT_REORDER8_STAY = 16, 17, 18, 19, 20
 EXPERIMENTS_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tools", "_variants", "libradixsort_hip_experiments.so")
@@ -52,7 +53,7 @@ SYMBOLS = [
     "rsx_create", "rsx_destroy", "rsx_set_stream", "rsx_get_stream", "rsx_set_option", "rsx_get_geometry", "rsx_resize",
     "rsx_upload", "rsx_fill_pad", "rsx_download", "rsx_pin_host", "rsx_unpin_host", "rsx_pipeline_submit", "rsx_pipeline_wait", "rsx_host_device_pointer",
     "rsx_histogram", "rsx_scan", "rsx_paste", "rsx_reorder", "rsx_sort", "rsx_sync", "rsx_check_status",
-    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_segmented_merge", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
+    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_segmented_merge", "rsx_segmented_set_op", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
 ]
 
 
@@ -166,6 +167,7 @@ def load_library() -> C.CDLL:
         "rsx_segmented_search": ([P, P, U64, P, U64, P, U64, P, C.c_uint32, P], I),
         "rsx_segmented_compact": ([P, P, U64, P, U64, P, P, C.c_uint32, P, P, P], I),
         "rsx_segmented_merge": ([P, P, P, U64, P, P, P, U64, P, U64, C.c_uint32, P, P, P, P], I),
+        "rsx_segmented_set_op": ([P, P, P, U64, P, P, P, U64, P, U64, C.c_uint32, C.c_uint32, P, P, P, P, P], I),
         "rsx_msd_count": ([P, P, U64, I, I, P], I),
         "rsx_msd_scatter": ([P, P, P, U64, P, P], I),
         "rsx_msd_plan": ([P, P, C.c_uint32, C.c_uint32, I, I, P], I),
@@ -556,6 +558,24 @@ class Engine:
         self._check(self.lib.rsx_segmented_merge(
             self._h, opt(d_a), opt(d_a_payload), na, opt(d_a_offsets), opt(d_b), opt(d_b_payload), nb, opt(d_b_offsets), num_segments, flags,
             opt(d_keys_out), opt(d_payload_out), opt(d_index_out), opt(d_out_offsets)), "rsx_segmented_merge")
+
+    def segmented_set_op(self, d_a: int | None, na: int, d_a_offsets: int | None, d_b: int | None, nb: int, d_b_offsets: int | None, num_segments: int,
+                         op: int, d_keys_out: int | None, d_out_offsets: int | None, d_index_out: int | None = None, d_match_out: int | None = None,
+                         d_a_payload: int | None = None, d_b_payload: int | None = None, d_payload_out: int | None = None, flags: int = 0) -> None:
+        """A set operation (op: SET_INTERSECTION, SET_DIFFERENCE - A minus B -, SET_UNION, SET_SYMMETRIC_DIFFERENCE) on sorted segment s
+        of A, d_a[aoff[s] .. aoff[s+1]), and sorted segment s of B, for every s, with std::set_*'s rule for duplicates: of a key that occurs
+        m times in A_s and n times in B_s the intersection keeps A's first min(m, n), the difference A's last max(m - n, 0), the union all
+        of A and B's last max(n - m, 0), the symmetric difference A's last max(m - n, 0) and B's last max(n - m, 0).  The kept elements come
+        in the stable merge's order, densely packed; d_out_offsets (num_segments + 1 uint64, required) gets the number kept before every
+        segment, d_index_out (uint32) the position in A_s ++ B_s, d_match_out (intersection only) the partner's position in B_s,
+        d_payload_out the 32-bit word that came with each key (the three payload pointers all or none).  Output buffers hold na elements
+        for intersection and difference, na + nb for the other two.  Both offsets None: ONE segment.  na + nb may exceed the capacity, the
+        engine's sort result is left alone, and has_payload does not matter.  Asynchronous on the engine's stream; bad offsets
+        (d_out_offsets holds zeros then, nothing else is written) are reported by the next sync() / check_status()."""
+        opt = lambda p: C.c_void_p(p) if p else None
+        self._check(self.lib.rsx_segmented_set_op(
+            self._h, opt(d_a), opt(d_a_payload), na, opt(d_a_offsets), opt(d_b), opt(d_b_payload), nb, opt(d_b_offsets), num_segments, op, flags,
+            opt(d_keys_out), opt(d_payload_out), opt(d_index_out), opt(d_match_out), opt(d_out_offsets)), "rsx_segmented_set_op")
 
     # -- exchange step of the sharded sort on the top B <= 8 bits ----------------
     def msd_count(self, d_keys: int, n: int, bits: int, world: int, d_counts: int) -> None:
@@ -1677,3 +1697,147 @@ def merge(a, b, payload_a=None, payload_b=None, descending: bool = False, return
     shape = tuple(a.shape[:-1]) + (la + lb,)
     res = (k.reshape(shape),) + ((p.reshape(shape),) if p is not None else ()) + ((idx.reshape(shape),) if return_index else ())
     return res[0] if len(res) == 1 else res
+
+
+# -- set operations on torch tensors ----------------------------------------------------------------------------------------------------
+_SET_OPS = {"intersection": SET_INTERSECTION, "difference": SET_DIFFERENCE, "union": SET_UNION, "symmetric_difference": SET_SYMMETRIC_DIFFERENCE}
+
+
+def _set_op_code(what: str, op) -> int:
+    if isinstance(op, str) and op in _SET_OPS:
+        return _SET_OPS[op]
+    if isinstance(op, int) and not isinstance(op, bool) and 0 <= op <= 3:
+        return op
+    raise ValueError(f"{what}: unknown op {op!r} (one of {', '.join(_SET_OPS)}, or SET_INTERSECTION .. SET_SYMMETRIC_DIFFERENCE)")
+
+
+def _setop_call(what: str, a, a_offsets, b, b_offsets, op, payload_a, payload_b, descending: bool, want_index: bool, want_match: bool):
+    """One rsx_segmented_set_op call on 1-D device tensors (both offsets None: one segment).  Returns (keys, out_offsets, payload, index,
+    match), trimmed to out_offsets[-1] (ONE host synchronisation)."""
+    import torch
+    for name, t in (("a", a), ("b", b)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{what}: {name} must be a tensor")
+    name = str(a.dtype).replace("torch.", "")
+    if name not in _KEY_DTYPES:
+        raise TypeError(f"{what}: unsupported key type {a.dtype}")
+    if b.dtype != a.dtype:
+        raise TypeError(f"{what}: a is {a.dtype}, b {b.dtype} (convert one of them: a set operation compares keys of one type)")
+    code = _set_op_code(what, op)
+    if want_match and code != SET_INTERSECTION:
+        raise ValueError(f"{what}: return_match belongs to the intersection (no other op pairs its outputs with b)")
+    if not a.is_cuda or not b.is_cuda:
+        raise ValueError(f"{what}: a and b must be device tensors (there is no CPU path)")
+    if a.dim() != 1 or b.dim() != 1 or b.device != a.device:
+        raise ValueError(f"{what}: a and b must be 1-D tensors on one device")
+    if (a_offsets is None) != (b_offsets is None):
+        raise ValueError(f"{what}: a_offsets and b_offsets must both be given or both be None")
+    for oname, o in (("a_offsets", a_offsets), ("b_offsets", b_offsets)):
+        if o is not None and (not torch.is_tensor(o) or o.dtype != torch.int64 or o.dim() != 1 or o.device != a.device):
+            raise ValueError(f"{what}: {oname} must be a 1-D int64 tensor on the keys' device")
+    if a_offsets is not None and a_offsets.numel() != b_offsets.numel():
+        raise ValueError(f"{what}: a_offsets and b_offsets must have the same number of entries")
+    if (payload_a is None) != (payload_b is None):
+        raise ValueError(f"{what}: payload_a and payload_b must both be given or both be None")
+    u32 = getattr(torch, "uint32", torch.int32)
+    for pname, p, k in (("payload_a", payload_a, a), ("payload_b", payload_b, b)):
+        if p is not None and (not torch.is_tensor(p) or p.shape != k.shape or p.device != k.device or p.dtype not in (torch.int32, u32)):
+            raise ValueError(f"{what}: {pname} must be an int32 / uint32 tensor shaped like its keys, on the same device")
+    if payload_a is not None and payload_a.dtype != payload_b.dtype:
+        raise ValueError(f"{what}: payload_a and payload_b must have one dtype")
+    na, nb = a.numel(), b.numel()
+    if na + nb > (1 << 31):
+        raise ValueError(f"{what}: at most 2^31 keys together (rsx_segmented_set_op's bound)")
+    nseg = 1 if a_offsets is None else max(a_offsets.numel() - 1, 0)
+    cap = na if code in (SET_INTERSECTION, SET_DIFFERENCE) else na + nb
+    dev = a.device
+    keys = torch.empty(cap, dtype=a.dtype, device=dev)
+    koff = torch.zeros(nseg + 1, dtype=torch.int64, device=dev)
+    pay = None if payload_a is None else torch.empty(cap, dtype=payload_a.dtype, device=dev)
+    index = torch.empty(cap, dtype=torch.int32, device=dev) if want_index else None
+    match = torch.empty(cap, dtype=torch.int32, device=dev) if want_match else None
+    total = 0
+    if na + nb > 0 and nseg > 0:
+        a_in, b_in = _aligned_copy(a, torch), _aligned_copy(b, torch)
+        cont = lambda t: None if t is None else t if t.is_contiguous() and t.data_ptr() % 8 == 0 else t.clone(memory_format=torch.contiguous_format)
+        ao, bo, pa, pb = cont(a_offsets), cont(b_offsets), cont(payload_a), cont(payload_b)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        device = dev.index if dev.index is not None else torch.cuda.current_device()
+        eng = _search_engine(device, torch.cuda.current_stream(dev).cuda_stream, name, bool(descending))
+        spare = None
+        if pay is not None:             # (an empty side or an empty output has no storage: a spare word stands in; it is neither read nor written)
+            spare = torch.empty(4, dtype=torch.int32, device=dev)
+            pa_ptr, pb_ptr, po_ptr = (pa.data_ptr() if na else spare.data_ptr()), (pb.data_ptr() if nb else spare.data_ptr()), (pay.data_ptr() if cap else spare.data_ptr())
+        else:
+            pa_ptr = pb_ptr = po_ptr = None
+        eng.segmented_set_op(ptr(a_in), na, ptr(ao), ptr(b_in), nb, ptr(bo), nseg, code, ptr(keys), koff.data_ptr(), ptr(index), ptr(match),
+                             d_a_payload=pa_ptr, d_b_payload=pb_ptr, d_payload_out=po_ptr)
+        total = int(koff[-1].item())            # the one read-back (a host synchronisation): how many were kept
+        eng.check_status()      # reports bad offsets of calls that have already finished
+    widen = lambda t: None if t is None else (t[:total].to(torch.int64) & 0xFFFFFFFF)
+    return keys[:total], koff, (None if pay is None else pay[:total]), widen(index), widen(match)
+
+
+def segmented_set_op(a, a_offsets, b, b_offsets, op, payload_a=None, payload_b=None, descending: bool = False, return_index: bool = False,
+                     return_match: bool = False):
+    """A set operation on sorted segment a[a_offsets[s] : a_offsets[s+1]] and sorted segment b[b_offsets[s] : b_offsets[s+1]], for every s, in
+    ONE engine call (rsx_segmented_set_op): returns (keys, out_offsets[, payload][, index][, match]).  op: "intersection", "difference"
+    (a minus b), "union", "symmetric_difference" (or the SET_* constants).  Duplicates follow std::set_*: of a key that occurs m times in
+    a's segment and n times in b's the intersection keeps a's first min(m, n), the difference a's last max(m - n, 0), the union all of a's
+    and b's last max(n - m, 0), the symmetric difference a's last max(m - n, 0) and b's last max(n - m, 0).  Keys are equal iff their bits
+    are (-0.0 and +0.0 differ; NaNs with equal bits are one key).  keys[out_offsets[s] : out_offsets[s+1]] holds segment s's kept elements
+    in the stable merge's order (a before equal b).  The segments must be sorted as this library sorts them (segmented_sort / sort_rows
+    with the same `descending`); inputs that are not sorted give an unspecified result.  payload_a / payload_b (int32 / uint32, both or
+    neither): the word that came with each key.  index (int64): the position of every kept element in the concatenation of its two
+    segments (below the a segment's length: from a).  match (int64, intersection only): the position in b's segment of the element a kept
+    element is paired with: a[a_offsets[s] + index] and b[b_offsets[s] + match] are an inner join.  The outputs are trimmed to
+    out_offsets[-1], which reads one int64 back: one host synchronisation per call.  Bad offsets raise RadixSortError."""
+    k, oo, p, idx, mt = _setop_call("segmented_set_op", a, a_offsets, b, b_offsets, op, payload_a, payload_b, descending, return_index, return_match)
+    return (k, oo) + ((p,) if p is not None else ()) + ((idx,) if return_index else ()) + ((mt,) if return_match else ())
+
+
+def _set_rows(what: str, op: int, a, b, payload_a, payload_b, descending: bool, return_index: bool, return_match: bool):
+    import torch
+    for name, t in (("a", a), ("b", b)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{what}: {name} must be a tensor")
+    if a.dim() == 0 or a.dim() != b.dim() or tuple(a.shape[:-1]) != tuple(b.shape[:-1]):
+        raise ValueError(f"{what}: a and b must have the same number of dimensions (at least one) and equal leading shape")
+    for pname, p, k in (("payload_a", payload_a, a), ("payload_b", payload_b, b)):
+        if p is not None and (not torch.is_tensor(p) or p.shape != k.shape):
+            raise ValueError(f"{what}: {pname} must be a tensor shaped like its keys")
+    la, lb = a.shape[-1], b.shape[-1]
+    flat = lambda t: None if t is None else t.contiguous().reshape(-1)
+    ao = bo = None
+    if a.dim() > 1:
+        rows = a.numel() // la if la else (b.numel() // lb if lb else 0)
+        steps = torch.arange(0, rows + 1, device=a.device, dtype=torch.int64)
+        ao, bo = steps * la, steps * lb
+    k, oo, p, idx, mt = _setop_call(what, flat(a), ao, flat(b), bo, op, flat(payload_a), flat(payload_b), descending, return_index, return_match)
+    res = (k,) + ((oo,) if a.dim() > 1 else ()) + ((p,) if p is not None else ()) + ((idx,) if return_index else ()) + ((mt,) if return_match else ())
+    return res[0] if len(res) == 1 else res
+
+
+def intersect_sorted(a, b, payload_a=None, payload_b=None, descending: bool = False, return_index: bool = False, return_match: bool = False):
+    """The multiset intersection of two sorted device tensors along their last dimension: 1-D inputs are one segment and the values come
+    back (then payload, index, match as asked for); N-D inputs with equal leading shape are intersected row by row, the rows being the
+    segments of ONE rsx_segmented_set_op call, and (values, row_offsets, ...) comes back: row r's result is
+    values[row_offsets[r] : row_offsets[r+1]].  The kept elements are a's; index are their columns in a, match their partners' columns in
+    b.  Order, duplicates, payloads and errors as segmented_set_op."""
+    return _set_rows("intersect_sorted", SET_INTERSECTION, a, b, payload_a, payload_b, descending, return_index, return_match)
+
+
+def difference_sorted(a, b, payload_a=None, payload_b=None, descending: bool = False, return_index: bool = False):
+    """The multiset difference a minus b of two sorted device tensors along their last dimension; shapes and results as intersect_sorted."""
+    return _set_rows("difference_sorted", SET_DIFFERENCE, a, b, payload_a, payload_b, descending, return_index, False)
+
+
+def union_sorted(a, b, payload_a=None, payload_b=None, descending: bool = False, return_index: bool = False):
+    """The multiset union of two sorted device tensors along their last dimension; shapes and results as intersect_sorted.  index: the
+    position in torch.cat([a, b], -1) of the row (below a's row length: from a)."""
+    return _set_rows("union_sorted", SET_UNION, a, b, payload_a, payload_b, descending, return_index, False)
+
+
+def symmetric_difference_sorted(a, b, payload_a=None, payload_b=None, descending: bool = False, return_index: bool = False):
+    """The multiset symmetric difference of two sorted device tensors along their last dimension; shapes, results and index as union_sorted."""
+    return _set_rows("symmetric_difference_sorted", SET_SYMMETRIC_DIFFERENCE, a, b, payload_a, payload_b, descending, return_index, False)

@@ -21,6 +21,7 @@
 #include "rsx_search.hpp"
 #include "rsx_compact.hpp"
 #include "rsx_merge.hpp"
+#include "rsx_setop.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -1250,6 +1251,7 @@ int sort_chain(rsx_engine* e, const SortJob& job)
 // synchronisation, so it is also looked at by the asynchronous calls — there it reports a time-out of work that has already
 // finished; the synchronising calls look after their hipStreamSynchronize.)  Reported once, then cleared: the engine stays usable.
 constexpr uint32_t kStatusCallMerge = 1;         // word 1 of the mapped status words: written by the call that reports, beside its segment in word 0
+constexpr uint32_t kStatusCallSetop = 2;
 int check_scan_timeout(rsx_engine* e, int status)
 {
     if (e->seg_status_host) {
@@ -1262,6 +1264,10 @@ int check_scan_timeout(rsx_engine* e, int status)
             *bad = 0;
             if (call == kStatusCallMerge)
                 return fail(status, ("rsx_segmented_merge: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n in d_a_offsets (n = na) or in "
+                                     "d_b_offsets (n = nb); d_out_offsets holds zeros and nothing else was written (the first such segment of the call; "
+                                     "reported once; the engine remains usable)").c_str());
+            if (call == kStatusCallSetop)
+                return fail(status, ("rsx_segmented_set_op: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n in d_a_offsets (n = na) or in "
                                      "d_b_offsets (n = nb); d_out_offsets holds zeros and nothing else was written (the first such segment of the call; "
                                      "reported once; the engine remains usable)").c_str());
             return fail(status, ("rsx_segmented_sort / rsx_segmented_topk / rsx_segmented_select: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; it was neither read nor "
@@ -2396,6 +2402,7 @@ int rsx_peer_enable(rsx_engine* e, int peer_device)
 #include "capi_search.inc"
 #include "capi_compact.inc"
 #include "capi_merge.inc"
+#include "capi_setop.inc"
 
 int rsx_key_range(rsx_engine* e, const void* d_keys, uint64_t n, uint64_t* lo, uint64_t* hi)
 {
