@@ -2,7 +2,7 @@
 // per tile of the global grid -> the flat table scan -> kept offsets -> survivors staged in LDS and stored.  Kernels: rsx_compact.hpp.
 // Nothing of the engine's sort state is read or written: the call needs the first-bad-segment word, the status word and one table entry
 // per tile (the segmented table and its group sums, grown on demand).
-// Included by rsx_capi.hip inside its extern "C" block, after capi_search.inc.
+// Included by rsx_capi.hip inside its extern "C" block, after capi_family.inc.
 
 extern "C++" {
 namespace {
@@ -25,48 +25,29 @@ int compact_enqueue(rsx_engine* e, const Key* keys, uint64_t n, const uint64_t* 
                     Key* kout, uint32_t* iout, uint64_t* koff)
 {
     if (!off) nseg = 1;
-    const uint64_t cus = e->num_cus > 0 ? static_cast<uint64_t>(e->num_cus) : 256u;
-    // launch bounds from n and the segment count alone: the table has one entry per tile of the global grid and one more (rsx_unique.hpp);
-    // a workgroup walks `chunk` consecutive tiles (more than one above cus * 16 tiles)
-    const uint32_t ntiles = static_cast<uint32_t>((n + rsx::kUniqTileKeys - 1) >> rsx::kUniqTileShift);
-    const uint32_t ntab = ntiles + 1;
-    const uint32_t npad = (ntab + rsx::kRadix - 1) / rsx::kRadix * rsx::kRadix;
-    const uint32_t nrow = npad / rsx::kRadix;                        // the scan kernels' "tiles": 16 rows of nrow entries = the flat table
-    const uint32_t ngroups = (nrow + rsx::kScanTiles - 1) / rsx::kScanTiles;
-    const uint32_t chunk = static_cast<uint32_t>((npad + cus * 16 - 1) / (cus * 16));
-    const uint32_t tgrid = (npad + chunk - 1) / chunk;
-    const uint32_t wgrid = (ntiles + chunk - 1) / chunk;
-    const uint32_t sgrid = static_cast<uint32_t>(std::min<uint64_t>((nseg + 1 + rsx::kUniqSmallThreads - 1) / rsx::kUniqSmallThreads, cus * 4));
-    int rc = ensure_segmented(e, SegShape{1, 0, 0}, 1);           // the status words; none of the sort's scratch
-    if (rc == RSX_OK) rc = seg_grow(e, &e->seg_table, &e->seg_table_cap, npad, "the per-tile table of the compaction");
-    if (rc == RSX_OK) rc = seg_grow(e, &e->seg_gsum, &e->seg_gsum_cap, static_cast<uint64_t>(rsx::kRadix) * ngroups, "the group sums");
-    if (rc == RSX_OK) rc = seg_grow(e, &e->seg_gsum2, &e->seg_gsum2_cap, static_cast<uint64_t>(rsx::kRadix) * ngroups, "the scanned group sums");
+    const uint64_t cus = cus_of(e);
+    const TileTable t = tile_table(n, rsx::kUniqTileShift, cus);
+    int rc = ensure_status_words(e);
+    if (rc == RSX_OK) rc = grow_tile_table(e, t, "the per-tile table of the compaction");
     if (rc != RSX_OK) return rc;
-    // (a launch, not a non-zero hipMemsetAsync: capi_unique.inc)
-    uint32_t* bad = e->seg_temp + 1;
-    hipLaunchKernelGGL(rsx::unique_reset_kernel, dim3(1), dim3(rsx::kWave), 0, e->stream, bad);
-    if (off) {
-        hipLaunchKernelGGL(rsx::unique_validate_kernel, dim3(sgrid), dim3(rsx::kUniqSmallThreads), 0, e->stream, off, nseg, n, bad);
-    }
+    uint32_t* bad = begin_offset_check(e, cus, nseg, off, n);
     Key a = 0, m = 0;
     order_consts<Key>(e, &a, &m);
     // 1. kept elements per tile, their flat exclusive scan, the kept offsets (which also report a bad segment)
     if (bounds) {
-        hipLaunchKernelGGL((rsx::compact_count_kernel<Key, true>), dim3(tgrid), dim3(rsx::kUniqThreads), 0, e->stream, keys, n, off, nseg, mask, bounds, flags, a,
-                           m, bad, e->seg_table, ntab, npad, chunk, koff);
+        hipLaunchKernelGGL((rsx::compact_count_kernel<Key, true>), dim3(t.tgrid), dim3(rsx::kUniqThreads), 0, e->stream, keys, n, off, nseg, mask, bounds, flags, a,
+                           m, bad, e->seg_table, t.ntab, t.npad, t.chunk, koff);
     } else {
-        hipLaunchKernelGGL((rsx::compact_count_kernel<Key, false>), dim3(tgrid), dim3(rsx::kUniqThreads), 0, e->stream, keys, n, off, nseg, mask, bounds, flags, a,
-                           m, bad, e->seg_table, ntab, npad, chunk, koff);
+        hipLaunchKernelGGL((rsx::compact_count_kernel<Key, false>), dim3(t.tgrid), dim3(rsx::kUniqThreads), 0, e->stream, keys, n, off, nseg, mask, bounds, flags, a,
+                           m, bad, e->seg_table, t.ntab, t.npad, t.chunk, koff);
     }
-    hipLaunchKernelGGL((rsx::scan_blocks_kernel<false, false>), dim3(ngroups), dim3(rsx::kScanTiles), 0, e->stream, e->seg_table, e->seg_gsum, nrow, ngroups,
-                       static_cast<uint32_t*>(nullptr));
-    hipLaunchKernelGGL(rsx::paste_scan_kernel, dim3(ngroups), dim3(rsx::kScanTiles), 0, e->stream, e->seg_table, e->seg_gsum, e->seg_gsum2, e->seg_temp, nrow,
-                       ngroups);
-    hipLaunchKernelGGL(rsx::unique_offsets_kernel, dim3(sgrid), dim3(rsx::kUniqSmallThreads), 0, e->stream, off, nseg, n, bad, e->seg_table, koff, e->seg_status, 1);
+    launch_table_scan(e, t.nrow, t.ngroups);
+    hipLaunchKernelGGL(rsx::unique_offsets_kernel, dim3(offsets_grid(nseg, cus)), dim3(rsx::kUniqSmallThreads), 0, e->stream, off, nseg, n, bad, e->seg_table, koff,
+                       e->seg_status, 1);
     // 2. the survivors, staged and stored
     if (kout || iout) {
-        if (bounds) compact_write_launch<Key, true>(e, wgrid, keys, n, off, nseg, mask, bounds, flags, a, m, bad, ntiles, chunk, koff, kout, iout);
-        else compact_write_launch<Key, false>(e, wgrid, keys, n, off, nseg, mask, bounds, flags, a, m, bad, ntiles, chunk, koff, kout, iout);
+        if (bounds) compact_write_launch<Key, true>(e, t.wgrid, keys, n, off, nseg, mask, bounds, flags, a, m, bad, t.ntiles, t.chunk, koff, kout, iout);
+        else compact_write_launch<Key, false>(e, t.wgrid, keys, n, off, nseg, mask, bounds, flags, a, m, bad, t.ntiles, t.chunk, koff, kout, iout);
     }
     RSX_TRY(hipGetLastError(), RSX_CALCULATION_FAILED);
     return RSX_OK;
@@ -92,33 +73,20 @@ int rsx_segmented_compact(rsx_engine* e, const void* d_keys, uint64_t n, const u
     const uint64_t kb = static_cast<uint64_t>(e->key_bytes);
     if (!d_keys || !aligned16(d_keys)) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_compact: keys must be a 16-byte aligned device pointer");
     if (!d_kept_offsets_out) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_compact: the kept-offsets output is required");
-    if ((reinterpret_cast<uintptr_t>(d_keys_out) % kb) != 0 || (reinterpret_cast<uintptr_t>(d_index_out) & 3u) != 0 ||
-        (reinterpret_cast<uintptr_t>(d_kept_offsets_out) & 7u) != 0)
+    if (!aligned(d_keys_out, kb) || !aligned(d_index_out, 4) || !aligned(d_kept_offsets_out, 8))
         return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_compact: the outputs must be aligned to their element size");
-    if ((reinterpret_cast<uintptr_t>(d_offsets) & 7u) != 0) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_compact: offsets must be an 8-byte aligned device pointer");
-    if ((reinterpret_cast<uintptr_t>(d_bounds) % kb) != 0) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_compact: bounds must be aligned to the key size");
+    if (!aligned(d_offsets, 8)) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_compact: offsets must be an 8-byte aligned device pointer");
+    if (!aligned(d_bounds, kb)) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_compact: bounds must be aligned to the key size");
     const uint64_t kbytes = n * kb, obytes = (num_segments + 1) * 8, ibytes = n * 4, bbytes = num_segments * kb;
-    const uint64_t ebytes = e->capacity * kb, epbytes = e->capacity * 4;
     const uint64_t kin_bytes = d_mask && !d_keys_out ? 0 : kbytes;       // a mask's keys are read for the key output only
-    const void* bufs[7] = {d_keys_out, d_index_out, d_kept_offsets_out, d_keys, d_offsets, d_mask, d_bounds};       // outputs first
-    const uint64_t bytes[7] = {kbytes, ibytes, obytes, kin_bytes, obytes, n, bbytes};
-    for (int b = 0; b < 7; ++b) {
-        for (int i = 0; i < 2; ++i) {
-            if (overlaps(bufs[b], bytes[b], e->keys[i], ebytes) || overlaps(bufs[b], bytes[b], e->perm[i], epbytes))
-                return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_compact: an input or output overlaps the engine's own buffers");
-        }
-    }
-    for (int a = 0; a < 3; ++a) {
-        for (int b = a + 1; b < 7; ++b) {
-            if (overlaps(bufs[a], bytes[a], bufs[b], bytes[b]))
-                return fail(RSX_HOST_BUFFERS_FAILED, b < 3 ? "rsx_segmented_compact: two outputs overlap"
-                                                           : "rsx_segmented_compact: an output overlaps an input (no operation is in place)");
-        }
-    }
+    if (check_buffers(e, "rsx_segmented_compact", {{d_keys_out, kbytes}, {d_index_out, ibytes}, {d_kept_offsets_out, obytes}},
+                      {{d_keys, kin_bytes}, {d_offsets, obytes}, {d_mask, n}, {d_bounds, bbytes}}) != RSX_OK)
+        return RSX_HOST_BUFFERS_FAILED;
     if (bind_device(e, RSX_CALCULATION_FAILED) != RSX_OK) return RSX_CALCULATION_FAILED;
     // (the engine's n, result and tables stay as they were: this call is no sort and uses none of the capacity-sized buffers)
-    return RSX_BY_KEY(e, (compact_enqueue<uint32_t>(e, static_cast<const uint32_t*>(d_keys), n, d_offsets, num_segments, d_mask, static_cast<const uint32_t*>(d_bounds),
-                                                    flags, static_cast<uint32_t*>(d_keys_out), d_index_out, d_kept_offsets_out)),
-                      (compact_enqueue<uint64_t>(e, static_cast<const uint64_t*>(d_keys), n, d_offsets, num_segments, d_mask, static_cast<const uint64_t*>(d_bounds),
-                                                 flags, static_cast<uint64_t*>(d_keys_out), d_index_out, d_kept_offsets_out)));
+    return by_key(e, [&](auto key) {
+        using Key = decltype(key);
+        return compact_enqueue<Key>(e, static_cast<const Key*>(d_keys), n, d_offsets, num_segments, d_mask, static_cast<const Key*>(d_bounds), flags,
+                                    static_cast<Key*>(d_keys_out), d_index_out, d_kept_offsets_out);
+    });
 }

@@ -1,7 +1,7 @@
 // capi_reduce.inc — C ABI of the reduce by key (rsx_segmented_reduce_by_key, include/radixsort_hip.h): the grouping steps of
 // rsx_segmented_unique (capi_unique.inc: sort with the positions as payload, or nothing in consecutive mode -> heads per tile -> the flat
 // table scan -> run offsets), then the values reduced per tile and carried across tiles -> counts.  Kernels: rsx_reduce.hpp.
-// Included by rsx_capi.hip inside its extern "C" block, after capi_unique.inc.
+// Included by rsx_capi.hip inside its extern "C" block, after capi_family.inc and capi_unique.inc (whose grouping steps it calls).
 
 extern "C++" {
 namespace {
@@ -77,49 +77,28 @@ int rsx_segmented_reduce_by_key(rsx_engine* e, const void* d_keys, const void* d
     const bool consecutive = (flags & RSX_UNIQUE_CONSECUTIVE) != 0;
     const uint64_t vb = (value_kind == RSX_VALUE_INT32 || value_kind == RSX_VALUE_FLOAT32) ? 4 : 8;
     if (!d_keys || !aligned16(d_keys)) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_reduce_by_key: keys must be a 16-byte aligned device pointer");
-    if (!d_values || (reinterpret_cast<uintptr_t>(d_values) % vb) != 0)
+    if (!d_values || !aligned(d_values, vb))
         return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_reduce_by_key: values must be a device pointer aligned to the value size");
     if (!d_keys_out || !d_run_offsets_out || !d_values_out)
         return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_reduce_by_key: the key, run-offset and value outputs are required");
-    if ((reinterpret_cast<uintptr_t>(d_keys_out) % e->key_bytes) != 0 || (reinterpret_cast<uintptr_t>(d_run_offsets_out) & 7u) != 0 ||
-        (reinterpret_cast<uintptr_t>(d_values_out) % vb) != 0 || (reinterpret_cast<uintptr_t>(d_counts_out) & 3u) != 0)
+    if (!aligned(d_keys_out, e->key_bytes) || !aligned(d_run_offsets_out, 8) || !aligned(d_values_out, vb) || !aligned(d_counts_out, 4))
         return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_reduce_by_key: the outputs must be aligned to their element size");
-    if (d_offsets && (reinterpret_cast<uintptr_t>(d_offsets) & 7u) != 0) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_reduce_by_key: offsets must be an 8-byte aligned device pointer");
+    if (!aligned(d_offsets, 8)) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_reduce_by_key: offsets must be an 8-byte aligned device pointer");
     if (!consecutive && !e->has_payload)
         return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_reduce_by_key: the positions of the values of a sorted call travel through the sort as its payload: "
                                              "they need an engine created with has_payload = 1");
     const uint64_t kbytes = n * static_cast<uint64_t>(e->key_bytes), obytes = (num_segments + 1) * 8, vbytes = n * vb, cbytes = n * 4;
-    const uint64_t ebytes = e->capacity * static_cast<uint64_t>(e->key_bytes), epbytes = e->capacity * 4;
-    const void* bufs[7] = {d_keys_out, d_run_offsets_out, d_values_out, d_counts_out, d_keys, d_values, d_offsets};       // outputs first
-    const uint64_t bytes[7] = {kbytes, obytes, vbytes, cbytes, kbytes, vbytes, obytes};
-    for (int b = 0; b < 7; ++b) {
-        for (int i = 0; i < 2; ++i) {
-            if (overlaps(bufs[b], bytes[b], e->keys[i], ebytes) || overlaps(bufs[b], bytes[b], e->perm[i], epbytes))
-                return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_reduce_by_key: an input or output overlaps the engine's own buffers");
-        }
-    }
-    for (int a = 0; a < 4; ++a) {
-        for (int b = a + 1; b < 7; ++b) {
-            if (overlaps(bufs[a], bytes[a], bufs[b], bytes[b]))
-                return fail(RSX_HOST_BUFFERS_FAILED, b < 4 ? "rsx_segmented_reduce_by_key: two outputs overlap" : "rsx_segmented_reduce_by_key: an output overlaps an input");
-        }
-    }
-    for (int a = 4; a < 6; ++a) {
-        for (int b = a + 1; b < 7; ++b) {
-            if (overlaps(bufs[a], bytes[a], bufs[b], bytes[b])) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_reduce_by_key: two inputs overlap");
-        }
-    }
+    if (check_buffers(e, "rsx_segmented_reduce_by_key", {{d_keys_out, kbytes}, {d_run_offsets_out, obytes}, {d_values_out, vbytes}, {d_counts_out, cbytes}},
+                      {{d_keys, kbytes}, {d_values, vbytes}, {d_offsets, obytes}}) != RSX_OK)
+        return RSX_HOST_BUFFERS_FAILED;
+    if (overlaps(d_keys, kbytes, d_values, vbytes) || overlaps(d_keys, kbytes, d_offsets, obytes) || overlaps(d_values, vbytes, d_offsets, obytes))
+        return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_reduce_by_key: two inputs overlap");
     if (bind_device(e, RSX_CALCULATION_FAILED) != RSX_OK) return RSX_CALCULATION_FAILED;
-    const int rc = RSX_BY_KEY(e,
-                              reduce_enqueue<uint32_t>(e, static_cast<const uint32_t*>(d_keys), d_values, n, d_offsets, num_segments, flags, op, value_kind,
-                                                       static_cast<uint32_t*>(d_keys_out), d_run_offsets_out, d_values_out, d_counts_out),
-                              reduce_enqueue<uint64_t>(e, static_cast<const uint64_t*>(d_keys), d_values, n, d_offsets, num_segments, flags, op, value_kind,
-                                                       static_cast<uint64_t*>(d_keys_out), d_run_offsets_out, d_values_out, d_counts_out));
-    // as after rsx_segmented_unique: the result lives in the caller's buffers only, and the engine's tables are not this call's
-    e->n = n;
-    e->result_external = true;
-    e->counted_keys = nullptr;
-    e->table_valid = false;
-    e->globsum_valid = false;
+    const int rc = by_key(e, [&](auto key) {
+        using Key = decltype(key);
+        return reduce_enqueue<Key>(e, static_cast<const Key*>(d_keys), d_values, n, d_offsets, num_segments, flags, op, value_kind, static_cast<Key*>(d_keys_out),
+                                   d_run_offsets_out, d_values_out, d_counts_out);
+    });
+    result_is_external(e, n);       // (whatever rc says: as rsx_segmented_unique)
     return rc;
 }

@@ -1,7 +1,7 @@
 // capi_scan.inc — C ABI of the scan by key (rsx_segmented_scan, include/radixsort_hip.h): validate the offsets -> tails per tile -> the
 // carries of all tiles (one workgroup) -> the tiles scanned and stored.  Kernels: rsx_scan_by_key.hpp.  Nothing of the engine's sort state
 // is read or written: the call needs the first-bad-segment word, the status word and 3 * tiles + 2 slots of per-tile scratch.
-// Included by rsx_capi.hip inside its extern "C" block, after capi_reduce.inc.
+// Included by rsx_capi.hip inside its extern "C" block, after capi_family.inc.
 
 extern "C++" {
 namespace {
@@ -28,26 +28,18 @@ int scan_enqueue(rsx_engine* e, const Key* keys, const void* values, uint64_t n,
                  uint32_t kind, void* vout)
 {
     if (!off) nseg = 1;
-    const uint64_t cus = e->num_cus > 0 ? static_cast<uint64_t>(e->num_cus) : 256u;
-    // launch bounds from n and the segment count alone; a workgroup walks `chunk` consecutive tiles (more than one above cus * 16 tiles)
+    const uint64_t cus = cus_of(e);
     const uint32_t ntiles = static_cast<uint32_t>((n + rsx::kUniqTileKeys - 1) >> rsx::kUniqTileShift);
-    const uint32_t chunk = static_cast<uint32_t>((ntiles + cus * 16 - 1) / (cus * 16));
-    const uint32_t tgrid = (ntiles + chunk - 1) / chunk;
-    int rc = ensure_segmented(e, SegShape{1, 0, 0}, 1);           // the status words; none of the sort's scratch
+    const TileChunks c = tile_chunks(ntiles, cus);
+    int rc = ensure_status_words(e);
     if (rc == RSX_OK) rc = seg_grow(e, &e->red_part, &e->red_part_cap, 3 * static_cast<uint64_t>(ntiles) + 2, "the per-tile partials of the scan");
     if (rc != RSX_OK) return rc;
-    // (a launch, not a non-zero hipMemsetAsync: capi_unique.inc)
-    uint32_t* bad = e->seg_temp + 1;
-    hipLaunchKernelGGL(rsx::unique_reset_kernel, dim3(1), dim3(rsx::kWave), 0, e->stream, bad);
-    if (off) {
-        const uint32_t sgrid = static_cast<uint32_t>(std::min<uint64_t>((nseg + 1 + rsx::kUniqSmallThreads - 1) / rsx::kUniqSmallThreads, cus * 4));
-        hipLaunchKernelGGL(rsx::unique_validate_kernel, dim3(sgrid), dim3(rsx::kUniqSmallThreads), 0, e->stream, off, nseg, n, bad);
-    }
+    uint32_t* bad = begin_offset_check(e, cus, nseg, off, n);
     switch (kind) {
-    case RSX_VALUE_INT32: scan_launch<Key, int32_t, KEYS>(e, keys, values, n, off, nseg, flags, op, vout, bad, ntiles, chunk, tgrid); break;
-    case RSX_VALUE_INT64: scan_launch<Key, int64_t, KEYS>(e, keys, values, n, off, nseg, flags, op, vout, bad, ntiles, chunk, tgrid); break;
-    case RSX_VALUE_FLOAT32: scan_launch<Key, float, KEYS>(e, keys, values, n, off, nseg, flags, op, vout, bad, ntiles, chunk, tgrid); break;
-    default: scan_launch<Key, double, KEYS>(e, keys, values, n, off, nseg, flags, op, vout, bad, ntiles, chunk, tgrid); break;
+    case RSX_VALUE_INT32: scan_launch<Key, int32_t, KEYS>(e, keys, values, n, off, nseg, flags, op, vout, bad, ntiles, c.chunk, c.grid); break;
+    case RSX_VALUE_INT64: scan_launch<Key, int64_t, KEYS>(e, keys, values, n, off, nseg, flags, op, vout, bad, ntiles, c.chunk, c.grid); break;
+    case RSX_VALUE_FLOAT32: scan_launch<Key, float, KEYS>(e, keys, values, n, off, nseg, flags, op, vout, bad, ntiles, c.chunk, c.grid); break;
+    default: scan_launch<Key, double, KEYS>(e, keys, values, n, off, nseg, flags, op, vout, bad, ntiles, c.chunk, c.grid); break;
     }
     RSX_TRY(hipGetLastError(), RSX_CALCULATION_FAILED);
     return RSX_OK;
@@ -69,29 +61,23 @@ int rsx_segmented_scan(rsx_engine* e, const void* d_keys, const void* d_values, 
     if (n > (1ull << 31)) return fail(RSX_CALCULATION_FAILED, "rsx_segmented_scan: at most 2^31 elements");
     const uint64_t vb = (value_kind == RSX_VALUE_INT32 || value_kind == RSX_VALUE_FLOAT32) ? 4 : 8;
     if (d_keys && !aligned16(d_keys)) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_scan: keys must be a 16-byte aligned device pointer (or NULL)");
-    if (!d_values || (reinterpret_cast<uintptr_t>(d_values) % vb) != 0)
+    if (!d_values || !aligned(d_values, vb))
         return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_scan: values must be a device pointer aligned to the value size");
-    if (!d_values_out || (reinterpret_cast<uintptr_t>(d_values_out) % vb) != 0)
+    if (!d_values_out || !aligned(d_values_out, vb))
         return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_scan: the output must be a device pointer aligned to the value size");
-    if (d_offsets && (reinterpret_cast<uintptr_t>(d_offsets) & 7u) != 0) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_scan: offsets must be an 8-byte aligned device pointer");
+    if (!aligned(d_offsets, 8)) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_scan: offsets must be an 8-byte aligned device pointer");
     const uint64_t kbytes = n * static_cast<uint64_t>(e->key_bytes), obytes = (num_segments + 1) * 8, vbytes = n * vb;
-    const uint64_t ebytes = e->capacity * static_cast<uint64_t>(e->key_bytes), epbytes = e->capacity * 4;
-    const void* bufs[4] = {d_values_out, d_values, d_keys, d_offsets};
-    const uint64_t bytes[4] = {vbytes, vbytes, kbytes, obytes};
-    for (int b = 0; b < 4; ++b) {
-        for (int i = 0; i < 2; ++i) {
-            if (overlaps(bufs[b], bytes[b], e->keys[i], ebytes) || overlaps(bufs[b], bytes[b], e->perm[i], epbytes))
-                return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_scan: an input or output overlaps the engine's own buffers");
-        }
-    }
     // in place (d_values_out == d_values exactly) is the one overlap that is served: a tile is read whole before it is written
-    if (d_values_out != d_values && overlaps(d_values_out, vbytes, d_values, vbytes))
+    const bool in_place = d_values_out == d_values;
+    if (!in_place && overlaps(d_values_out, vbytes, d_values, vbytes))
         return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_scan: the output overlaps the values without being the same pointer (in place means d_values_out == d_values)");
-    if (overlaps(d_values_out, vbytes, d_keys, kbytes) || overlaps(d_values_out, vbytes, d_offsets, obytes))
-        return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_scan: the output overlaps the keys or the offsets");
+    if (check_buffers(e, "rsx_segmented_scan", {{d_values_out, vbytes}}, {{in_place ? nullptr : d_values, vbytes}, {d_keys, kbytes}, {d_offsets, obytes}}) != RSX_OK)
+        return RSX_HOST_BUFFERS_FAILED;
     if (bind_device(e, RSX_CALCULATION_FAILED) != RSX_OK) return RSX_CALCULATION_FAILED;
     // (the engine's n, result and tables stay as they were: this call is no sort and uses none of the capacity-sized buffers)
     if (!d_keys) return scan_enqueue<uint32_t, false>(e, nullptr, d_values, n, d_offsets, num_segments, flags, op, value_kind, d_values_out);
-    return RSX_BY_KEY(e, (scan_enqueue<uint32_t, true>(e, static_cast<const uint32_t*>(d_keys), d_values, n, d_offsets, num_segments, flags, op, value_kind, d_values_out)),
-                      (scan_enqueue<uint64_t, true>(e, static_cast<const uint64_t*>(d_keys), d_values, n, d_offsets, num_segments, flags, op, value_kind, d_values_out)));
+    return by_key(e, [&](auto key) {
+        using Key = decltype(key);
+        return scan_enqueue<Key, true>(e, static_cast<const Key*>(d_keys), d_values, n, d_offsets, num_segments, flags, op, value_kind, d_values_out);
+    });
 }

@@ -1,7 +1,7 @@
 // capi_select.inc — C ABI of the segmented select (rsx_segmented_select, include/radixsort_hip.h): the segmented sort's classify chain ->
 // small segments sorted in LDS (the image slots named by the ranks stored) -> radix select over the tiles of all large segments for up
 // to 8 ranks per segment at once, a tie count per tile, the table scan, and a locate pass.  Kernels: rsx_select.hpp.
-// Included by rsx_capi.hip inside its extern "C" block, after capi_topk.inc (whose group sizing and scratch fields it shares).
+// Included by rsx_capi.hip inside its extern "C" block, after capi_family.inc and capi_topk.inc (whose group sizing and scratch fields it shares).
 
 extern "C++" {
 namespace {
@@ -42,10 +42,7 @@ void select_large_launch(rsx_engine* e, const Key* kin, uint32_t R, uint32_t gti
     }
     hipLaunchKernelGGL((rsx::select_count_kernel<Key, RC>), dim3(tgrid), dim3(rsx::kTopkThreads), 0, e->stream, kin, e->seg_table, e->seg_hdr,
                        e->seg_large, e->seg_tstart, e->topk_state, R, both);
-    hipLaunchKernelGGL((rsx::scan_blocks_kernel<false, false>), dim3(ngroups), dim3(rsx::kScanTiles), 0, e->stream, e->seg_table, e->seg_gsum, ntab,
-                       ngroups, static_cast<uint32_t*>(nullptr));
-    hipLaunchKernelGGL(rsx::paste_scan_kernel, dim3(ngroups), dim3(rsx::kScanTiles), 0, e->stream, e->seg_table, e->seg_gsum, e->seg_gsum2, e->seg_temp,
-                       ntab, ngroups);
+    launch_table_scan(e, ntab, ngroups);
     hipLaunchKernelGGL((rsx::select_locate_kernel<Key>), dim3(tgrid), dim3(rsx::kTopkThreads), 0, e->stream, kin, e->seg_table, e->seg_hdr, e->seg_large,
                        e->seg_tstart, e->topk_state, R, kout, iout, both);
 }
@@ -55,7 +52,7 @@ int select_enqueue(rsx_engine* e, const Key* kin, uint64_t n, const uint64_t* of
                    uint32_t* iout)
 {
     const SegShape s = seg_shape(n, nseg);
-    const uint64_t cus = e->num_cus > 0 ? static_cast<uint64_t>(e->num_cus) : 256u;
+    const uint64_t cus = cus_of(e);
     const uint32_t gtiles = topk_group_tiles(s, cus);
     int rc = ensure_segmented(e, s, nseg);
     if (rc == RSX_OK) rc = ensure_select(e, s, gtiles, R);
@@ -82,18 +79,10 @@ int select_enqueue(rsx_engine* e, const Key* kin, uint64_t n, const uint64_t* of
     RSX_TRY(hipGetLastError(), RSX_CALCULATION_FAILED);
 
     // 2. small segments: one workgroup per segment, every pass in LDS, the ranked image slots stored
-    {
-        const uint64_t min_len[rsx::kSegClasses] = {2, rsx::kSegClass0Max + 1, rsx::kSegClass1Max + 1};
-        const uint64_t per_cu[rsx::kSegClasses] = {32, 16, 4};
-        for (int c = 0; c < rsx::kSegClasses; ++c) {
-            const uint64_t grid = std::min<uint64_t>({nseg, n / min_len[c], cus * per_cu[c]});
-            if (grid == 0) continue;
-            if (c == 0) select_sort_launch<Key, 64, 4>(e, grid, kin, ranks, R, kout, iout, off, c, both);
-            else if (c == 1) select_sort_launch<Key, 64, 16>(e, grid, kin, ranks, R, kout, iout, off, c, both);
-            else select_sort_launch<Key, 256, 16>(e, grid, kin, ranks, R, kout, iout, off, c, both);
-        }
-        RSX_TRY(hipGetLastError(), RSX_CALCULATION_FAILED);
-    }
+    for_each_small_class(nseg, n, cus, [&](int c, uint64_t grid, auto shape) {
+        select_sort_launch<Key, decltype(shape)::THREADS, decltype(shape)::KPT>(e, grid, kin, ranks, R, kout, iout, off, c, both);
+    });
+    RSX_TRY(hipGetLastError(), RSX_CALCULATION_FAILED);
 
     // 3. large segments: select rounds for all R ranks at once, tie counts per tile, the table scan, locate
     if (s.max_large) {
@@ -128,41 +117,20 @@ int rsx_segmented_select(rsx_engine* e, const void* d_keys, uint64_t n, const ui
         return fail(RSX_CALCULATION_FAILED, "rsx_segmented_select: too many keys for one table scan");
     if (!d_keys || !aligned16(d_keys)) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_select: keys must be a 16-byte aligned device pointer");
     if (!d_keys_out || !d_index_out) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_select: no output buffer");
-    if ((reinterpret_cast<uintptr_t>(d_keys_out) % e->key_bytes) != 0 || (reinterpret_cast<uintptr_t>(d_index_out) & 3u) != 0)
+    if (!aligned(d_keys_out, e->key_bytes) || !aligned(d_index_out, 4))
         return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_select: the outputs must be aligned to their element size");
-    if (!d_offsets || (reinterpret_cast<uintptr_t>(d_offsets) & 7u) != 0) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_select: offsets must be an 8-byte aligned device pointer");
-    if (!d_ranks || (reinterpret_cast<uintptr_t>(d_ranks) & 3u) != 0) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_select: ranks must be a 4-byte aligned device pointer");
+    if (!d_offsets || !aligned(d_offsets, 8)) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_select: offsets must be an 8-byte aligned device pointer");
+    if (!d_ranks || !aligned(d_ranks, 4)) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_select: ranks must be a 4-byte aligned device pointer");
     const uint64_t kbytes = n * static_cast<uint64_t>(e->key_bytes), obytes = (num_segments + 1) * 8, rbytes = num_segments * R * 4;
     const uint64_t okbytes = num_segments * R * static_cast<uint64_t>(e->key_bytes), oibytes = num_segments * R * 4;
-    const uint64_t ebytes = e->capacity * static_cast<uint64_t>(e->key_bytes), epbytes = e->capacity * 4;
-    for (int i = 0; i < 2; ++i) {
-        const void* eb[2] = {e->keys[i], e->perm[i]};
-        const uint64_t eby[2] = {ebytes, epbytes};
-        for (int j = 0; j < 2; ++j) {
-            if (overlaps(d_keys, kbytes, eb[j], eby[j]) || overlaps(d_keys_out, okbytes, eb[j], eby[j]) || overlaps(d_index_out, oibytes, eb[j], eby[j]) ||
-                overlaps(d_offsets, obytes, eb[j], eby[j]) || overlaps(d_ranks, rbytes, eb[j], eby[j]))
-                return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_select: an input or output overlaps the engine's own buffers");
-        }
-    }
-    const void* outs[2] = {d_keys_out, d_index_out};
-    const uint64_t outb[2] = {okbytes, oibytes};
-    for (int j = 0; j < 2; ++j) {
-        if (overlaps(outs[j], outb[j], d_keys, kbytes) || overlaps(outs[j], outb[j], d_offsets, obytes) || overlaps(outs[j], outb[j], d_ranks, rbytes))
-            return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_select: an output overlaps an input");
-    }
-    if (overlaps(d_keys_out, okbytes, d_index_out, oibytes)) return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_select: the key and index outputs overlap");
+    if (check_buffers(e, "rsx_segmented_select", {{d_keys_out, okbytes}, {d_index_out, oibytes}}, {{d_keys, kbytes}, {d_offsets, obytes}, {d_ranks, rbytes}}) != RSX_OK)
+        return RSX_HOST_BUFFERS_FAILED;
     if (bind_device(e, RSX_CALCULATION_FAILED) != RSX_OK) return RSX_CALCULATION_FAILED;
-    const int rc = RSX_BY_KEY(e,
-                              select_enqueue<uint32_t>(e, static_cast<const uint32_t*>(d_keys), n, d_offsets, num_segments, d_ranks, R,
-                                                       static_cast<uint32_t*>(d_keys_out), d_index_out),
-                              select_enqueue<uint64_t>(e, static_cast<const uint64_t*>(d_keys), n, d_offsets, num_segments, d_ranks, R,
-                                                       static_cast<uint64_t*>(d_keys_out), d_index_out));
+    const int rc = by_key(e, [&](auto key) {
+        using Key = decltype(key);
+        return select_enqueue<Key>(e, static_cast<const Key*>(d_keys), n, d_offsets, num_segments, d_ranks, R, static_cast<Key*>(d_keys_out), d_index_out);
+    });
     if (rc != RSX_OK) return rc;
-    // as after rsx_segmented_topk: the result lives in the caller's buffers only, and the engine's tables are not this call's
-    e->n = n;
-    e->result_external = true;
-    e->counted_keys = nullptr;
-    e->table_valid = false;
-    e->globsum_valid = false;
+    result_is_external(e, n);
     return RSX_OK;
 }

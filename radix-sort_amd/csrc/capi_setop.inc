@@ -3,7 +3,7 @@
 // -> the kept elements ranked in LDS and stored.  Kernels: rsx_setop.hpp.  Nothing of the engine's sort state is read or written: the call
 // needs the first-bad-segment word, the status words, one 8-byte split per tile boundary and one table entry per tile (the merge's splits
 // and the compaction's table and group sums, grown on demand, outside stream captures).
-// Included by rsx_capi.hip inside its extern "C" block, after capi_merge.inc.
+// Included by rsx_capi.hip inside its extern "C" block, after capi_family.inc and capi_merge.inc (whose status ids it continues).
 
 extern "C++" {
 namespace {
@@ -28,51 +28,31 @@ template <typename Key>
 int setop_enqueue(rsx_engine* e, const Key* ka, const uint32_t* pa, uint64_t na, const uint64_t* aoff, const Key* kb, const uint32_t* pb, uint64_t nb,
                   const uint64_t* boff, uint64_t nseg, uint32_t op, uint64_t cap, Key* kout, uint32_t* pout, uint32_t* iout, uint32_t* mout, uint64_t* koff)
 {
-    const uint64_t cus = e->num_cus > 0 ? static_cast<uint64_t>(e->num_cus) : 256u;
-    // launch bounds from na + nb and the segment count alone: the merge's tiles of 4096 merged positions, the compaction's table of one
-    // entry per tile and one more; a workgroup walks `chunk` consecutive tiles (more than one above cus * 16 tiles)
-    const uint32_t ntiles = static_cast<uint32_t>((na + nb + rsx::kMergeTileKeys - 1) >> rsx::kMergeTileShift);
-    const uint32_t ntab = ntiles + 1;
-    const uint32_t npad = (ntab + rsx::kRadix - 1) / rsx::kRadix * rsx::kRadix;
-    const uint32_t nrow = npad / rsx::kRadix;
-    const uint32_t ngroups = (nrow + rsx::kScanTiles - 1) / rsx::kScanTiles;
-    const uint32_t chunk = static_cast<uint32_t>((npad + cus * 16 - 1) / (cus * 16));
-    const uint32_t tgrid = (npad + chunk - 1) / chunk;
-    const uint32_t wgrid = (ntiles + chunk - 1) / chunk;
-    const uint32_t sgrid = static_cast<uint32_t>(std::min<uint64_t>((nseg + 1 + rsx::kUniqSmallThreads - 1) / rsx::kUniqSmallThreads, cus * 4));
-    const uint64_t split_items = std::max<uint64_t>(static_cast<uint64_t>(ntiles) + 1, nseg + 1);
+    const uint64_t cus = cus_of(e);
+    // the merge's tiles of 4096 merged positions, the compaction's table of one entry per tile and one more
+    const TileTable t = tile_table(na + nb, rsx::kMergeTileShift, cus);
+    const uint64_t split_items = std::max<uint64_t>(static_cast<uint64_t>(t.ntiles) + 1, nseg + 1);
     const uint32_t pgrid = static_cast<uint32_t>(std::min<uint64_t>((split_items + rsx::kMergeSplitThreads - 1) / rsx::kMergeSplitThreads, cus * 16));
-    int rc = ensure_segmented(e, SegShape{1, 0, 0}, 1);           // the status words; none of the sort's scratch
-    if (rc == RSX_OK) rc = seg_grow(e, &e->merge_split, &e->merge_split_cap, static_cast<uint64_t>(ntiles) + 1, "the per-tile splits of the set operation");
-    if (rc == RSX_OK) rc = seg_grow(e, &e->seg_table, &e->seg_table_cap, npad, "the per-tile table of the set operation");
-    if (rc == RSX_OK) rc = seg_grow(e, &e->seg_gsum, &e->seg_gsum_cap, static_cast<uint64_t>(rsx::kRadix) * ngroups, "the group sums");
-    if (rc == RSX_OK) rc = seg_grow(e, &e->seg_gsum2, &e->seg_gsum2_cap, static_cast<uint64_t>(rsx::kRadix) * ngroups, "the scanned group sums");
+    int rc = ensure_status_words(e);
+    if (rc == RSX_OK) rc = seg_grow(e, &e->merge_split, &e->merge_split_cap, static_cast<uint64_t>(t.ntiles) + 1, "the per-tile splits of the set operation");
+    if (rc == RSX_OK) rc = grow_tile_table(e, t, "the per-tile table of the set operation");
     if (rc != RSX_OK) return rc;
-    // (a launch, not a non-zero hipMemsetAsync: capi_unique.inc)
-    uint32_t* bad = e->seg_temp + 1;
-    hipLaunchKernelGGL(rsx::unique_reset_kernel, dim3(1), dim3(rsx::kWave), 0, e->stream, bad);
-    if (aoff) {
-        hipLaunchKernelGGL(rsx::unique_validate_kernel, dim3(sgrid), dim3(rsx::kUniqSmallThreads), 0, e->stream, aoff, nseg, na, bad);
-        hipLaunchKernelGGL(rsx::unique_validate_kernel, dim3(sgrid), dim3(rsx::kUniqSmallThreads), 0, e->stream, boff, nseg, nb, bad);
-    }
+    uint32_t* bad = begin_offset_check(e, cus, nseg, aoff, na, boff, nb);
     Key a = 0, m = 0;
     order_consts<Key>(e, &a, &m);
     const rsx::MergeOffsets o{aoff, boff, na, nb, 0, 0};
     // the merge's split, unchanged; it writes no offsets here (the kept offsets are this call's) and reports a bad segment under this call's id
     hipLaunchKernelGGL((rsx::merge_split_kernel<Key>), dim3(pgrid), dim3(rsx::kMergeSplitThreads), 0, e->stream, ka, kb, o, nseg, a, m, bad, e->seg_status,
-                       kStatusCallSetop, ntiles, e->merge_split, static_cast<uint64_t*>(nullptr));
+                       kStatusCallSetop, t.ntiles, e->merge_split, static_cast<uint64_t*>(nullptr));
     const rsx::SetopArgs<Key> g{ka, pa, kb, pb, o, nseg, a, m, op, e->merge_split};
     // 1. kept elements per tile, their flat exclusive scan, the kept offsets (zeros on a bad segment)
-    hipLaunchKernelGGL((rsx::setop_count_kernel<Key>), dim3(tgrid), dim3(rsx::kMergeThreads), 0, e->stream, g, bad, e->seg_table, ntab, npad, chunk, koff);
-    hipLaunchKernelGGL((rsx::scan_blocks_kernel<false, false>), dim3(ngroups), dim3(rsx::kScanTiles), 0, e->stream, e->seg_table, e->seg_gsum, nrow, ngroups,
-                       static_cast<uint32_t*>(nullptr));
-    hipLaunchKernelGGL(rsx::paste_scan_kernel, dim3(ngroups), dim3(rsx::kScanTiles), 0, e->stream, e->seg_table, e->seg_gsum, e->seg_gsum2, e->seg_temp, nrow,
-                       ngroups);
-    hipLaunchKernelGGL(rsx::setop_offsets_kernel, dim3(sgrid), dim3(rsx::kUniqSmallThreads), 0, e->stream, o, nseg, bad, e->seg_table, cap, koff);
+    hipLaunchKernelGGL((rsx::setop_count_kernel<Key>), dim3(t.tgrid), dim3(rsx::kMergeThreads), 0, e->stream, g, bad, e->seg_table, t.ntab, t.npad, t.chunk, koff);
+    launch_table_scan(e, t.nrow, t.ngroups);
+    hipLaunchKernelGGL(rsx::setop_offsets_kernel, dim3(offsets_grid(nseg, cus)), dim3(rsx::kUniqSmallThreads), 0, e->stream, o, nseg, bad, e->seg_table, cap, koff);
     // 2. the kept elements, ranked and stored
     if (kout || pout || iout || mout) {
-        if (pout) setop_write_launch<Key, true>(e, wgrid, g, bad, ntiles, chunk, static_cast<uint32_t>(cap), kout, pout, iout, mout);
-        else setop_write_launch<Key, false>(e, wgrid, g, bad, ntiles, chunk, static_cast<uint32_t>(cap), kout, pout, iout, mout);
+        if (pout) setop_write_launch<Key, true>(e, t.wgrid, g, bad, t.ntiles, t.chunk, static_cast<uint32_t>(cap), kout, pout, iout, mout);
+        else setop_write_launch<Key, false>(e, t.wgrid, g, bad, t.ntiles, t.chunk, static_cast<uint32_t>(cap), kout, pout, iout, mout);
     }
     RSX_TRY(hipGetLastError(), RSX_CALCULATION_FAILED);
     return RSX_OK;
@@ -103,39 +83,24 @@ int rsx_segmented_set_op(rsx_engine* e, const void* d_a, const uint32_t* d_a_pay
     const uint64_t kb = static_cast<uint64_t>(e->key_bytes);
     if ((na > 0 && !d_a) || (nb > 0 && !d_b) || !aligned16(d_a) || !aligned16(d_b))
         return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_set_op: d_a and d_b must be 16-byte aligned device pointers");
-    if ((reinterpret_cast<uintptr_t>(d_a_payload) & 3u) != 0 || (reinterpret_cast<uintptr_t>(d_b_payload) & 3u) != 0 ||
-        (reinterpret_cast<uintptr_t>(d_payload_out) & 3u) != 0 || (reinterpret_cast<uintptr_t>(d_index_out) & 3u) != 0 ||
-        (reinterpret_cast<uintptr_t>(d_match_out) & 3u) != 0 || (reinterpret_cast<uintptr_t>(d_keys_out) % kb) != 0)
+    if (!aligned(d_a_payload, 4) || !aligned(d_b_payload, 4) || !aligned(d_payload_out, 4) || !aligned(d_index_out, 4) || !aligned(d_match_out, 4) ||
+        !aligned(d_keys_out, kb))
         return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_set_op: the payloads and the outputs must be aligned to their element size");
-    if ((reinterpret_cast<uintptr_t>(d_a_offsets) & 7u) != 0 || (reinterpret_cast<uintptr_t>(d_b_offsets) & 7u) != 0 ||
-        (reinterpret_cast<uintptr_t>(d_out_offsets) & 7u) != 0)
+    if (!aligned(d_a_offsets, 8) || !aligned(d_b_offsets, 8) || !aligned(d_out_offsets, 8))
         return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_set_op: offsets must be 8-byte aligned device pointers");
     // what the caller provides: na elements for what only A can supply, na + nb otherwise
     const uint64_t cap = op == RSX_SET_INTERSECTION || op == RSX_SET_DIFFERENCE ? na : na + nb;
     const uint64_t obytes = (num_segments + 1) * 8;
-    const uint64_t ebytes = e->capacity * kb, epbytes = e->capacity * 4;
-    const void* bufs[11] = {d_keys_out, d_payload_out, d_index_out, d_match_out, d_out_offsets, d_a, d_b, d_a_payload, d_b_payload, d_a_offsets, d_b_offsets};       // outputs first
-    const uint64_t bytes[11] = {cap * kb, cap * 4, cap * 4, cap * 4, obytes, na * kb, nb * kb, na * 4, nb * 4, obytes, obytes};
-    for (int b = 0; b < 11; ++b) {
-        for (int i = 0; i < 2; ++i) {
-            if (overlaps(bufs[b], bytes[b], e->keys[i], ebytes) || overlaps(bufs[b], bytes[b], e->perm[i], epbytes))
-                return fail(RSX_HOST_BUFFERS_FAILED, "rsx_segmented_set_op: an input or output overlaps the engine's own buffers");
-        }
-    }
-    for (int a = 0; a < 5; ++a) {
-        for (int b = a + 1; b < 11; ++b) {
-            if (overlaps(bufs[a], bytes[a], bufs[b], bytes[b]))
-                return fail(RSX_HOST_BUFFERS_FAILED, b < 5 ? "rsx_segmented_set_op: two outputs overlap"
-                                                           : "rsx_segmented_set_op: an output overlaps an input (there is no in-place form)");
-        }
-    }
+    if (check_buffers(e, "rsx_segmented_set_op",
+                      {{d_keys_out, cap * kb}, {d_payload_out, cap * 4}, {d_index_out, cap * 4}, {d_match_out, cap * 4}, {d_out_offsets, obytes}},
+                      {{d_a, na * kb}, {d_b, nb * kb}, {d_a_payload, na * 4}, {d_b_payload, nb * 4}, {d_a_offsets, obytes}, {d_b_offsets, obytes}}) != RSX_OK)
+        return RSX_HOST_BUFFERS_FAILED;
     if (na + nb == 0 || num_segments == 0) return RSX_OK;
     if (bind_device(e, RSX_CALCULATION_FAILED) != RSX_OK) return RSX_CALCULATION_FAILED;
     // (the engine's n, result and tables stay as they were: this call is no sort and uses none of the capacity-sized buffers)
-    return RSX_BY_KEY(e, (setop_enqueue<uint32_t>(e, static_cast<const uint32_t*>(d_a), d_a_payload, na, d_a_offsets, static_cast<const uint32_t*>(d_b), d_b_payload,
-                                                  nb, d_b_offsets, num_segments, op, cap, static_cast<uint32_t*>(d_keys_out), d_payload_out, d_index_out, d_match_out,
-                                                  d_out_offsets)),
-                      (setop_enqueue<uint64_t>(e, static_cast<const uint64_t*>(d_a), d_a_payload, na, d_a_offsets, static_cast<const uint64_t*>(d_b), d_b_payload,
-                                               nb, d_b_offsets, num_segments, op, cap, static_cast<uint64_t*>(d_keys_out), d_payload_out, d_index_out, d_match_out,
-                                               d_out_offsets)));
+    return by_key(e, [&](auto key) {
+        using Key = decltype(key);
+        return setop_enqueue<Key>(e, static_cast<const Key*>(d_a), d_a_payload, na, d_a_offsets, static_cast<const Key*>(d_b), d_b_payload, nb, d_b_offsets,
+                                  num_segments, op, cap, static_cast<Key*>(d_keys_out), d_payload_out, d_index_out, d_match_out, d_out_offsets);
+    });
 }

@@ -22,6 +22,7 @@
 #include "rsx_compact.hpp"
 #include "rsx_merge.hpp"
 #include "rsx_setop.hpp"
+#include "rsx_args.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -1282,16 +1283,9 @@ int check_scan_timeout(rsx_engine* e, int status)
     }
     return RSX_OK;
 }
-bool aligned16(const void* p)
-{
-    return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
-}
-
-bool overlaps(const void* a, uint64_t abytes, const void* b, uint64_t bbytes)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a && b && abytes && bbytes && a0 < b0 + bbytes && b0 < a0 + abytes;
-}
+using rsx_args::aligned;       // rsx_args.hpp: the address arithmetic of the argument checks
+using rsx_args::aligned16;
+using rsx_args::overlaps;
 
 // How a caller's device range relates to one of the engine's two ping-pong buffers:
 // 0 = disjoint from both, 1 = starts exactly at buffer *which (the pointer rsx_result_device hands out), -1 = any other overlap.
@@ -2392,6 +2386,7 @@ int rsx_peer_enable(rsx_engine* e, int peer_device)
     return RSX_OK;
 }
 
+#include "capi_family.inc"
 #include "capi_msd.inc"
 #include "capi_segmented.inc"
 #include "capi_topk.inc"

@@ -39,6 +39,14 @@ def test_host_selftest_binary():
     assert "checks passed" in proc.stdout
 
 
+def test_args_selftest_binary():
+    """csrc/rsx_args.hpp (overlap and alignment arithmetic, the buffer rules of the segmented family) under plain g++, on made-up addresses"""
+    exe = os.path.join(HOST, "bin", "args_selftest")
+    proc = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert proc.returncode == 0, proc.stdout + proc.stderr
+    assert "checks passed" in proc.stdout
+
+
 def test_product_datasets_match_reference_goldens(hostlib, oracle, golden):
     # same inputs as the reference's generators (golden digests come from its Dataset.h)
     for row in golden["datasets"]:
