@@ -623,6 +623,44 @@ int rsx_segmented_set_op(rsx_engine* e, const void* d_a, const uint32_t* d_a_pay
                          uint64_t num_segments, uint32_t op, uint32_t flags /* must be 0 */,
                          void* d_keys_out /* or NULL */, uint32_t* d_payload_out /* or NULL */, uint32_t* d_index_out /* or NULL */,
                          uint32_t* d_match_out /* or NULL; intersection only */, uint64_t* d_out_offsets);
+/* rsx_segmented_histogram: the keys of every segment counted per bin (cub::DeviceHistogram; torch.bincount, torch.histc and
+ *   torch.histogram, with ragged rows).  Segment s is d_keys[off[s] .. off[s+1]); d_offsets == NULL is the one segment [0, n).
+ *   RESULT.  d_counts_out holds S x B uint32 counters, row-major: d_counts_out[s * B + b] = the keys of segment s that fall into bin b.  Every
+ *   one of the S * B entries is written by every accepted call that launches, zeros included: the call zeroes them itself.  Keys that
+ *   fall into no bin are dropped.  Nothing else is written.  Bins are numbered in the ENGINE's order, in both forms.
+ *   EDGES FORM (d_edges != NULL): B + 1 keys of the engine's key kind in device memory, sorted in the engine's order (IEEE 754 totalOrder
+ *   for floats, descending on a descending engine), shared by all segments; 1 <= B <= 4096.  With j the RSX_SEARCH_RIGHT position of key k
+ *   in the edges (what rsx_segmented_search returns): bin j - 1 if 1 <= j <= B; bin B - 1 if j == B + 1 and k has the bits of edges[B]
+ *   (the last bin is closed on both sides); dropped otherwise.  On an ascending engine that is numpy.histogram(x, bins=edges).  Keys are
+ *   equal iff their bits are: -0.0 and +0.0 are different edges and a NaN is an ordinary key.  Edges that are not sorted give unspecified
+ *   counts; every key is still counted at most once and no access leaves the buffers.  lo_bits, hi_bits and width_shift must be 0.
+ *   EVEN FORM, INTEGER KEY KINDS (d_edges == NULL): lo = the key whose bits are the low key_bytes of lo_bits.  Key k goes to bin
+ *   (k - lo) >> width_shift if k does not come before lo in ascending value order and that bin is < B (the arithmetic runs on the
+ *   order-mapped unsigned words: right for signed keys).  width_shift = 0, lo = 0 is torch.bincount(x, minlength=B)[:B].
+ *   width_shift < 8 * key_bytes; hi_bits must be 0.  On a descending engine bin b becomes B - 1 - b.
+ *   EVEN FORM, FLOAT KEY KINDS: lo and hi from lo_bits and hi_bits, both finite, lo < hi; width_shift must be 0.  With scale =
+ *   Key(B) / (hi - lo) computed once on the host in the key's own precision (refused unless finite and positive), key x goes to bin
+ *   min(B - 1, floor((x - lo) * scale)) if lo <= x && x <= hi by IEEE comparison: -0.0 counts as 0.0; NaN and out-of-range keys are
+ *   dropped, as torch.histc drops them.  The subtraction and the multiplication are each rounded once.  Results with a subnormal x - lo
+ *   are unspecified.  On a descending engine bin b becomes B - 1 - b.
+ *   HOW.  One kernel zeroes the counters; one kernel walks tiles of 4096 keys.  Up to 4096 bins a workgroup counts in LDS (a copy per wave
+ *   up to 1024 bins), keeps counting from tile to tile while the segment stays the same, and adds its non-zero counters to the result
+ *   when the segment changes and at its end.  More bins, and the pieces of segments shorter than 256 keys, add to the result directly.
+ *   Counts are integers: the result does not depend on the order of the additions.  Bytes: n keys read, 8 per counter.
+ *   THE ENGINE'S SORT STATE IS UNTOUCHED, whatever the engine's has_payload: n may exceed the capacity and an earlier sort's result stays
+ *   valid; no scratch grows.  Asynchronous on the engine's stream, nothing read back, capturable once the engine's status words exist (any
+ *   earlier call of the segmented family).  Offsets are validated on the device: with a bad segment (off[s+1] < off[s] or off[s+1] > n)
+ *   all S * B counters are zero and the next rsx_sync / rsx_check_status reports RSX_CALCULATION_FAILED once, naming this call and the
+ *   first such segment; the engine stays usable.
+ *   REFUSED AT ONCE: RSX_CALCULATION_FAILED for a null engine, flags != 0, num_bins == 0, more than 4096 bins in the edges form, the
+ *   parameter combinations ruled out above, 2^32 - 1 segments or more, n > 2^31, num_segments * num_bins > 2^31;
+ *   RSX_HOST_BUFFERS_FAILED for a null d_keys with n > 0 or one that is not 16-byte aligned, edges not aligned to the key size, a null
+ *   d_counts_out or one not 4-byte aligned, offsets not 8-byte aligned, the counters overlapping an input, anything overlapping the
+ *   engine's buffers.  n == 0 with a valid shape STILL ZEROES the counters (rsx_segmented_compact launches nothing then; here an all-zero
+ *   histogram is the right answer).  d_offsets != NULL with num_segments == 0 returns RSX_OK and writes nothing. */
+int rsx_segmented_histogram(rsx_engine* e, const void* d_keys, uint64_t n, const uint64_t* d_offsets /* or NULL */, uint64_t num_segments,
+                            const void* d_edges /* or NULL */, uint64_t lo_bits, uint64_t hi_bits, uint32_t width_shift, uint64_t num_bins,
+                            uint32_t flags /* must be 0 */, uint32_t* d_counts_out);
 /* Receive buffers other ranks can write to (the peer-store exchange below): rsx_peer_alloc (hipMalloc + an IPC handle to hand to the other
  * PROCESSES, which map it with rsx_peer_open / rsx_peer_close — peer access over xGMI); ranks that are threads of one process use the
  * pointer itself (after rsx_peer_enable, once per other device). */

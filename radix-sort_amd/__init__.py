@@ -53,7 +53,7 @@ SYMBOLS = [
     "rsx_create", "rsx_destroy", "rsx_set_stream", "rsx_get_stream", "rsx_set_option", "rsx_get_geometry", "rsx_resize",
     "rsx_upload", "rsx_fill_pad", "rsx_download", "rsx_pin_host", "rsx_unpin_host", "rsx_pipeline_submit", "rsx_pipeline_wait", "rsx_host_device_pointer",
     "rsx_histogram", "rsx_scan", "rsx_paste", "rsx_reorder", "rsx_sort", "rsx_sync", "rsx_check_status",
-    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_segmented_merge", "rsx_segmented_set_op", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
+    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_segmented_merge", "rsx_segmented_set_op", "rsx_segmented_histogram", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
 ]
 
 
@@ -168,6 +168,7 @@ def load_library() -> C.CDLL:
         "rsx_segmented_compact": ([P, P, U64, P, U64, P, P, C.c_uint32, P, P, P], I),
         "rsx_segmented_merge": ([P, P, P, U64, P, P, P, U64, P, U64, C.c_uint32, P, P, P, P], I),
         "rsx_segmented_set_op": ([P, P, P, U64, P, P, P, U64, P, U64, C.c_uint32, C.c_uint32, P, P, P, P, P], I),
+        "rsx_segmented_histogram": ([P, P, U64, P, U64, P, U64, U64, C.c_uint32, U64, C.c_uint32, P], I),
         "rsx_msd_count": ([P, P, U64, I, I, P], I),
         "rsx_msd_scatter": ([P, P, P, U64, P, P], I),
         "rsx_msd_plan": ([P, P, C.c_uint32, C.c_uint32, I, I, P], I),
@@ -576,6 +577,28 @@ class Engine:
         self._check(self.lib.rsx_segmented_set_op(
             self._h, opt(d_a), opt(d_a_payload), na, opt(d_a_offsets), opt(d_b), opt(d_b_payload), nb, opt(d_b_offsets), num_segments, op, flags,
             opt(d_keys_out), opt(d_payload_out), opt(d_index_out), opt(d_match_out), opt(d_out_offsets)), "rsx_segmented_set_op")
+
+    def key_bits(self, value) -> int:
+        """The bit pattern of the Python number `value` as a key of this engine (two's complement for integers, IEEE 754 for floats)."""
+        if self.key_kind == KEY_FLOAT:
+            return int(np.array(value, dtype=self.dtype).view(np.uint32 if self.dtype.itemsize == 4 else np.uint64))
+        return int(value) & ((1 << (8 * self.dtype.itemsize)) - 1)
+
+    def segmented_histogram(self, d_keys: int | None, n: int, d_offsets: int | None, num_segments: int, num_bins: int, d_counts_out: int,
+                            d_edges: int | None = None, lo=0, hi=0, width_shift: int = 0) -> None:
+        """The keys of every segment [off[s], off[s+1]) counted per bin into d_counts_out (num_segments x num_bins uint32, row-major; the
+        call zeroes them itself; keys that fall into no bin are dropped).  d_edges (num_bins + 1 keys sorted in the engine's order, at most
+        4096 bins): bin j holds edges[j] <= k < edges[j+1] in that order, the last bin closed on both sides: numpy.histogram(x, bins=edges)
+        on an ascending engine.  Without edges, integer keys: bin (k - lo) >> width_shift (lo = 0, width_shift = 0: bincount); float keys:
+        bin min(num_bins - 1, floor((x - lo) * (num_bins / (hi - lo)))) for lo <= x <= hi, NaN dropped (histc).  lo and hi are Python
+        numbers.  A descending engine numbers the even forms' bins backwards.  d_offsets None: ONE segment [0, n).  n may exceed the
+        capacity and the engine's sort result is left alone.  Asynchronous on the engine's stream; bad offsets (every counter is zero
+        then) are reported by the next sync() / check_status()."""
+        opt = lambda p: C.c_void_p(p) if p else None
+        even = not d_edges
+        self._check(self.lib.rsx_segmented_histogram(
+            self._h, opt(d_keys), n, opt(d_offsets), num_segments, opt(d_edges), self.key_bits(lo) if even else int(lo),
+            self.key_bits(hi) if even else int(hi), width_shift, num_bins, 0, opt(d_counts_out)), "rsx_segmented_histogram")
 
     # -- exchange step of the sharded sort on the top B <= 8 bits ----------------
     def msd_count(self, d_keys: int, n: int, bits: int, world: int, d_counts: int) -> None:
@@ -1596,6 +1619,206 @@ def compact_rows(x, mask=None, bound=None, strict: bool = False, invert: bool = 
         b = bound.expand(x.shape[:-1]).contiguous().reshape(-1)
     v, ko, idx = _compact_call("compact_rows", flat, offsets, m, b, strict, invert, descending, False, True, return_index)
     return (v, ko) + ((idx,) if return_index else ())
+
+
+# -- histograms on torch tensors --------------------------------------------------------------------------------------------------------
+_INT_KEY_DTYPES = ("uint32", "int32", "uint64", "int64")
+_HIST_MAX_COUNTERS = 1 << 31
+
+
+def _hist_call(what: str, keys, offsets, nseg: int, bins, lo, hi, width_shift: int, descending: bool):
+    """One rsx_segmented_histogram call on a 1-D device tensor (offsets None: one segment): the counters as an int64 tensor [nseg, B].
+    bins: an int (even form) or a 1-D tensor of B + 1 edges of the keys' dtype.  Reads nothing back."""
+    import torch
+    name = _compact_keys_check(what, keys)
+    edges = None
+    if torch.is_tensor(bins):
+        if bins.dtype != keys.dtype:
+            raise TypeError(f"{what}: the edges are {bins.dtype}, the keys {keys.dtype} (convert one of them: the bins are compared as keys of one type)")
+        if bins.dim() != 1 or bins.numel() < 2 or bins.device != keys.device:
+            raise ValueError(f"{what}: the edges must be a 1-D tensor of at least 2 entries on the keys' device")
+        if bins.numel() - 1 > 4096:
+            raise ValueError(f"{what}: at most 4096 bins in the edges form (use searchsorted, then bincount)")
+        if lo is not None or hi is not None or width_shift:
+            raise ValueError(f"{what}: lo, hi and width_shift belong to the even form (bins an int)")
+        edges = bins.contiguous()
+        nb = edges.numel() - 1
+    else:
+        nb = int(bins)
+        if nb < 1:
+            raise ValueError(f"{what}: at least one bin")
+        if name in _INT_KEY_DTYPES:
+            if hi is not None:
+                raise ValueError(f"{what}: hi belongs to float keys (integer keys: lo and width_shift)")
+            lo = 0 if lo is None else lo
+        elif lo is None or hi is None:
+            raise ValueError(f"{what}: float keys need lo and hi in the even form")
+    n = keys.numel()
+    if n > (1 << 31) or nseg * nb > _HIST_MAX_COUNTERS:
+        raise ValueError(f"{what}: at most 2^31 elements and 2^31 counters (rsx_segmented_histogram's bounds)")
+    dev = keys.device
+    counts = torch.zeros((nseg, nb), dtype=torch.int32, device=dev)
+    if nseg > 0:
+        k_in = _aligned_copy(keys, torch)
+        off = None
+        if offsets is not None:
+            off = offsets if offsets.is_contiguous() and offsets.data_ptr() % 8 == 0 else offsets.clone(memory_format=torch.contiguous_format)
+        device = dev.index if dev.index is not None else torch.cuda.current_device()
+        eng = _search_engine(device, torch.cuda.current_stream(dev).cuda_stream, name, bool(descending))
+        eng.segmented_histogram(k_in.data_ptr() if n else None, n, off.data_ptr() if off is not None else None, nseg, nb, counts.data_ptr(),
+                                d_edges=edges.data_ptr() if edges is not None else None, lo=lo or 0, hi=hi or 0, width_shift=int(width_shift))
+        eng.check_status()      # reports bad offsets of calls that have already finished; no synchronisation
+    return counts.to(torch.int64) & 0xFFFFFFFF
+
+
+def segmented_histogram(keys, offsets, bins, lo=None, hi=None, width_shift: int = 0, descending: bool = False):
+    """The keys of every segment [offsets[s], offsets[s+1]) of the 1-D device tensor `keys` counted per bin in ONE engine call
+    (rsx_segmented_histogram): an int64 tensor [S, B].  bins a 1-D tensor of B + 1 edges of the keys' dtype, sorted in this library's
+    order (floats: IEEE 754 totalOrder, -0.0 before +0.0; descending=True: descending), at most 4096 bins: numpy.histogram(x, bins=edges)
+    per segment, the last bin closed on both sides.  bins an int: integer keys go to bin (k - lo) >> width_shift (lo defaults to 0),
+    float keys to bin min(B - 1, floor((x - lo) * (B / (hi - lo)))) for lo <= x <= hi; descending=True numbers those bins backwards.
+    Keys that fall into no bin are dropped.  offsets None: one segment.  Never synchronises with the host; bad offsets (all counters are
+    zero then) raise RadixSortError at a later call or synchronisation of the engine."""
+    import torch
+    _compact_keys_check("segmented_histogram", keys)
+    if keys.dim() != 1:
+        raise ValueError("segmented_histogram: keys must be a 1-D device tensor")
+    if offsets is not None and (offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.device != keys.device):
+        raise ValueError("segmented_histogram: offsets must be a 1-D int64 tensor on the keys' device (or None: one segment)")
+    nseg = 1 if offsets is None else max(offsets.numel() - 1, 0)
+    return _hist_call("segmented_histogram", keys, offsets, nseg, bins, lo, hi, width_shift, descending)
+
+
+def _hist_int_check(what: str, x) -> str:
+    import torch
+    if torch.is_tensor(x) and str(x.dtype).replace("torch.", "") not in _INT_KEY_DTYPES:
+        raise TypeError(f"{what}: the input must be an integer tensor (int32, int64, uint32 or uint64), not {x.dtype}")
+    return _compact_keys_check(what, x)
+
+
+def bincount(x, minlength: int = 0, num_bins=None):
+    """torch.bincount(x, minlength=minlength) without weights on a 1-D integer device tensor: int64 counts of max(x) + 1 entries, at least
+    minlength.  The length needs max(x): ONE read-back (Engine.key_range), as torch has one; negative values raise ValueError there.
+    num_bins given: exactly max(num_bins, minlength) counters, values from there on and negative ones are dropped, and nothing is read
+    back: no host synchronisation.  Weights are out of scope (a float atomic sum depends on arrival order; see reduce_by_key)."""
+    import torch
+    name = _hist_int_check("bincount", x)
+    if x.dim() != 1:
+        raise ValueError("bincount: x must be a 1-D device tensor")
+    if minlength < 0:
+        raise ValueError("bincount: minlength must be non-negative")
+    if num_bins is not None:
+        nb = max(int(num_bins), int(minlength))
+    elif x.numel() == 0:
+        nb = int(minlength)
+    else:
+        k_in = _aligned_copy(x, torch)
+        dev = x.device
+        device = dev.index if dev.index is not None else torch.cuda.current_device()
+        eng = _search_engine(device, torch.cuda.current_stream(dev).cuda_stream, name, False)
+        lo, hi = eng.key_range(k_in.data_ptr(), k_in.numel())          # of key ^ sign bit for signed keys: the one read-back
+        sign = (1 << (8 * _KEY_DTYPES[name][0] - 1)) if _KEY_DTYPES[name][1] == KEY_SIGNED else 0
+        if lo < sign:
+            raise ValueError("bincount: the input holds negative values")
+        nb = max(hi - sign + 1, int(minlength))
+        x = k_in
+    if nb == 0:
+        return torch.zeros(0, dtype=torch.int64, device=x.device)
+    if nb > _HIST_MAX_COUNTERS:
+        raise ValueError("bincount: at most 2^31 bins (rsx_segmented_histogram's bound)")
+    return _hist_call("bincount", x, None, 1, nb, 0, None, 0, False).reshape(-1)
+
+
+def bincount_rows(ids, num_bins: int):
+    """bincount of every row of the integer device tensor `ids` along its last dimension, in ONE rsx_segmented_histogram call: int64
+    counts [..., num_bins]; ids outside [0, num_bins) are dropped.  No host synchronisation.  (torch.bincount is 1-D only.)"""
+    import torch
+    _hist_int_check("bincount_rows", ids)
+    if ids.dim() == 0:
+        raise ValueError("bincount_rows: ids must be a device tensor with at least one dimension")
+    cols = ids.shape[-1]
+    rows = ids.numel() // cols if cols else int(np.prod(ids.shape[:-1], dtype=np.int64))
+    offsets = torch.arange(0, rows + 1, device=ids.device, dtype=torch.int64) * cols
+    res = _hist_call("bincount_rows", ids.contiguous().reshape(-1), offsets, rows, int(num_bins), 0, None, 0, False)
+    return res.reshape(tuple(ids.shape[:-1]) + (int(num_bins),))
+
+
+def _hist_float_range(what: str, x, lo, hi):
+    """(lo, hi) of an even float histogram: the caller's, or - lo == hi - the data's range (ONE read-back; torch.aminmax, because
+    Engine.key_range refuses float engines), widened by 1 either side when empty: torch.histc's rule."""
+    import torch
+    lo, hi = float(lo), float(hi)
+    if lo == hi and x.numel() > 0:
+        mn, mx = torch.aminmax(x)
+        lo, hi = float(mn), float(mx)
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError(f"{what}: the range [{lo}, {hi}] is not finite")
+    if lo > hi:
+        raise ValueError(f"{what}: max must be larger than min")
+    if lo == hi:
+        lo, hi = lo - 1.0, hi + 1.0
+    return lo, hi
+
+
+def _hist_float_check(what: str, x) -> str:
+    import torch
+    if torch.is_tensor(x) and x.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{what}: the input must be a float32 or float64 tensor, not {x.dtype}")
+    return _compact_keys_check(what, x)
+
+
+def histc(x, bins: int = 100, min=0, max=0):
+    """torch.histc(x, bins=bins, min=min, max=max) on a float32 / float64 device tensor of any shape: the counts of `bins` equal-width
+    bins over [min, max] as a tensor of x's dtype; elements outside the range and NaNs are dropped; min == max takes the data's range (one
+    read-back).  The bin of x is min(bins - 1, floor((x - min) * (bins / (max - min)))), each operation rounded once in x's precision:
+    for values and ranges that are exact in that arithmetic this is torch's result; elsewhere the two may differ in a few bins, as
+    torch and numpy do."""
+    import torch
+    _hist_float_check("histc", x)
+    lo, hi = _hist_float_range("histc", x, min, max)
+    return _hist_call("histc", x.contiguous().reshape(-1), None, 1, int(bins), lo, hi, 0, False).reshape(-1).to(x.dtype)
+
+
+def histogram(x, bins, range=None):
+    """torch.histogram(x, bins, range=range) without weights and density on a device tensor: (counts int64, bin_edges).  bins a 1-D tensor
+    of edges of x's dtype (any of the six key dtypes; ascending in this library's order; at most 4096 bins): numpy.histogram(x,
+    bins=edges).  bins an int (float dtypes): equal-width bins over range = (lo, hi), or over the data's range (one read-back);
+    bin_edges = torch.linspace(lo, hi, bins + 1); the bin arithmetic is histc's."""
+    import torch
+    if torch.is_tensor(bins):
+        _compact_keys_check("histogram", x)
+        if range is not None:
+            raise ValueError("histogram: range belongs to an int bins")
+        return _hist_call("histogram", x.contiguous().reshape(-1), None, 1, bins, None, None, 0, False).reshape(-1), bins
+    _hist_float_check("histogram", x)
+    lo, hi = _hist_float_range("histogram", x, *(range if range is not None else (0, 0)))
+    counts = _hist_call("histogram", x.contiguous().reshape(-1), None, 1, int(bins), lo, hi, 0, False).reshape(-1)
+    return counts, torch.linspace(lo, hi, int(bins) + 1, dtype=x.dtype, device=x.device)
+
+
+def histogram_rows(x, bins, range=None):
+    """histogram of every row of the device tensor x along its last dimension, in ONE rsx_segmented_histogram call: (counts int64
+    [..., B], bin_edges).  bins and range as histogram; the edges or the range are shared by all rows (an int bins without a range takes
+    the range of the whole tensor)."""
+    import torch
+    if x.dim() == 0:
+        raise ValueError("histogram_rows: x must be a device tensor with at least one dimension")
+    if torch.is_tensor(bins):
+        _compact_keys_check("histogram_rows", x)
+        if range is not None:
+            raise ValueError("histogram_rows: range belongs to an int bins")
+        lo = hi = None
+        edges, nb = bins, bins.numel() - 1
+    else:
+        _hist_float_check("histogram_rows", x)
+        lo, hi = _hist_float_range("histogram_rows", x, *(range if range is not None else (0, 0)))
+        nb = int(bins)
+        edges = torch.linspace(lo, hi, nb + 1, dtype=x.dtype, device=x.device)
+    cols = x.shape[-1]
+    rows = x.numel() // cols if cols else int(np.prod(x.shape[:-1], dtype=np.int64))
+    offsets = torch.arange(0, rows + 1, device=x.device, dtype=torch.int64) * cols
+    res = _hist_call("histogram_rows", x.contiguous().reshape(-1), offsets, rows, bins if torch.is_tensor(bins) else nb, lo, hi, 0, False)
+    return res.reshape(tuple(x.shape[:-1]) + (nb,)), edges
 
 
 # -- merge on torch tensors -------------------------------------------------------------------------------------------------------------

@@ -22,6 +22,7 @@
 #include "rsx_compact.hpp"
 #include "rsx_merge.hpp"
 #include "rsx_setop.hpp"
+#include "rsx_bins.hpp"
 #include "rsx_args.hpp"
 
 #include <hip/hip_runtime.h>
@@ -1253,6 +1254,7 @@ int sort_chain(rsx_engine* e, const SortJob& job)
 // finished; the synchronising calls look after their hipStreamSynchronize.)  Reported once, then cleared: the engine stays usable.
 constexpr uint32_t kStatusCallMerge = 1;         // word 1 of the mapped status words: written by the call that reports, beside its segment in word 0
 constexpr uint32_t kStatusCallSetop = 2;
+constexpr uint32_t kStatusCallHistogram = 3;
 int check_scan_timeout(rsx_engine* e, int status)
 {
     if (e->seg_status_host) {
@@ -1271,6 +1273,9 @@ int check_scan_timeout(rsx_engine* e, int status)
                 return fail(status, ("rsx_segmented_set_op: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n in d_a_offsets (n = na) or in "
                                      "d_b_offsets (n = nb); d_out_offsets holds zeros and nothing else was written (the first such segment of the call; "
                                      "reported once; the engine remains usable)").c_str());
+            if (call == kStatusCallHistogram)
+                return fail(status, ("rsx_segmented_histogram: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; every counter of "
+                                     "d_counts_out is zero (the first such segment of the call; reported once; the engine remains usable)").c_str());
             return fail(status, ("rsx_segmented_sort / rsx_segmented_topk / rsx_segmented_select: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; it was neither read nor "
                                  "written (the first such segment of the call; reported once; the engine remains usable)").c_str());
         }
@@ -2398,6 +2403,7 @@ int rsx_peer_enable(rsx_engine* e, int peer_device)
 #include "capi_compact.inc"
 #include "capi_merge.inc"
 #include "capi_setop.inc"
+#include "capi_histogram.inc"
 
 int rsx_key_range(rsx_engine* e, const void* d_keys, uint64_t n, uint64_t* lo, uint64_t* hi)
 {
