@@ -661,6 +661,43 @@ int rsx_segmented_set_op(rsx_engine* e, const void* d_a, const uint32_t* d_a_pay
 int rsx_segmented_histogram(rsx_engine* e, const void* d_keys, uint64_t n, const uint64_t* d_offsets /* or NULL */, uint64_t num_segments,
                             const void* d_edges /* or NULL */, uint64_t lo_bits, uint64_t hi_bits, uint32_t width_shift, uint64_t num_bins,
                             uint32_t flags /* must be 0 */, uint32_t* d_counts_out);
+/* rsx_segmented_reduce: SUM, MIN, MAX, ARGMIN or ARGMAX of the values of every segment (cub::DeviceSegmentedReduce; torch.segment_reduce;
+ *   x.sum(-1), amax, argmax over the rows of a batch).  Nothing is sorted and there are no keys: the engine's key kind does not matter.
+ *   RESULT.  d_values_out[s] = op over v[off[s] .. off[s+1]) for EVERY s < S: dense by segment id, not packed.  d_offsets == NULL is the
+ *   one segment [0, n), and num_segments must be 1 then.  Values are n entries of RSX_VALUE_INT32, _INT64, _FLOAT32 or _FLOAT64, aligned
+ *   to their size; only positions in [off[0], off[S]) are read.  Integer sums wrap (two's complement); float MIN / MAX give NaN if the
+ *   segment holds one, as rsx_segmented_reduce_by_key does.
+ *   EMPTY SEGMENTS get the op's identity: 0 for SUM, the type's largest value (+inf for floats) for MIN and ARGMIN, its smallest (-inf)
+ *   for MAX and ARGMAX; their index is 0xFFFFFFFF.
+ *   ARGMIN / ARGMAX.  d_index_out[s] is the position, relative to off[s], of the FIRST element that attains the extreme.  A NaN beats
+ *   every number and among NaNs the first wins (torch.argmax); -0.0 and +0.0 tie and the first wins.  d_values_out, if given, gets the
+ *   value at that position with its bits unchanged.  d_index_out is required for the two arg ops and must be NULL for SUM, MIN and MAX.
+ *   WHAT IS WRITTEN.  Every accepted call with valid offsets writes all S results (and all S indices), also with n == 0 and with
+ *   off[0] == off[S], as rsx_segmented_histogram writes all its counters.  num_segments == 0 (with offsets) launches and writes nothing.
+ *   FLOAT SUMS ARE BITWISE REPRODUCIBLE.  d_values_out[s] is a function of values, offsets and n alone, through the elements' places on
+ *   the grid of 4096-element tiles and the places of the segment boundaries (the association is written at the top of rsx_segreduce.hpp:
+ *   a thread folds its 16 elements left to right, a flagged Hillis-Steele scan joins the 64 lanes of a wave, the four wave totals are
+ *   folded left to right — the levels of rsx_segmented_scan, the same code, so a segment inside one tile gets the bits the inclusive
+ *   scan stores at its last element — and a fixed join runs across the tiles of a longer segment).  It does not depend on the grid size,
+ *   the tiles per workgroup, the engine's capacity, the stream, or eager or captured execution.  That is a contract.  No atomic touches a
+ *   value and no workgroup waits for another: two launches in stream order after the offsets' check (one fold per tile, then the empty
+ *   segments and the segments that cross tile edges), one read of the values.
+ *   THE ENGINE'S SORT STATE IS UNTOUCHED, as with rsx_segmented_scan: the call uses none of the capacity-sized buffers (only per-tile
+ *   scratch grows, outside stream captures), so n may exceed the capacity and an earlier sort's result stays valid.  n <= 2^31, fewer
+ *   than 2^32 - 1 segments.  Asynchronous on the engine's stream, nothing read back, every launch sized from n and num_segments,
+ *   capturable once a call of this size has run.  Offsets are validated on the device: with a bad segment (off[s+1] < off[s] or
+ *   off[s+1] > n) NOTHING is written and the next rsx_sync / rsx_check_status reports RSX_CALCULATION_FAILED once, naming this call and
+ *   the first such segment; the engine stays usable.
+ *   REFUSED AT ONCE: RSX_CALCULATION_FAILED for a null engine, flags != 0, an unknown op or value kind, d_offsets == NULL with
+ *   num_segments != 1, 2^32 - 1 segments or more, n > 2^31; RSX_HOST_BUFFERS_FAILED for a null d_values with n > 0 or one not aligned
+ *   to the value size, a null d_values_out for SUM / MIN / MAX or a misaligned one, a null or misaligned d_index_out for the arg ops or
+ *   a given one for the others, offsets not 8-byte aligned, an output overlapping an input or the other output, anything overlapping
+ *   the engine's buffers. */
+#define RSX_REDUCE_ARGMIN 3
+#define RSX_REDUCE_ARGMAX 4   /* RSX_REDUCE_SUM / _MIN / _MAX keep 0 / 1 / 2; the two arg ops are rsx_segmented_reduce's only */
+int rsx_segmented_reduce(rsx_engine* e, const void* d_values, uint64_t n, const uint64_t* d_offsets /* or NULL */, uint64_t num_segments,
+                         uint32_t flags /* must be 0 */, uint32_t op, uint32_t value_kind, void* d_values_out /* or NULL for the arg ops */,
+                         uint32_t* d_index_out /* arg ops only */);
 /* Receive buffers other ranks can write to (the peer-store exchange below): rsx_peer_alloc (hipMalloc + an IPC handle to hand to the other
  * PROCESSES, which map it with rsx_peer_open / rsx_peer_close — peer access over xGMI); ranks that are threads of one process use the
  * pointer itself (after rsx_peer_enable, once per other device). */

@@ -38,6 +38,7 @@ OPT_DESCENDING = 21
 KEY_UNSIGNED, KEY_SIGNED, KEY_FLOAT = 0, 1, 2
 UNIQUE_CONSECUTIVE = 1     # RSX_UNIQUE_CONSECUTIVE: flags bit 0 of rsx_segmented_unique and rsx_segmented_reduce_by_key
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2                                   # RSX_REDUCE_*: op of rsx_segmented_reduce_by_key
+REDUCE_ARGMIN, REDUCE_ARGMAX = 3, 4                                            # ... and the two that rsx_segmented_reduce adds
 VALUE_INT32, VALUE_INT64, VALUE_FLOAT32, VALUE_FLOAT64 = 0, 1, 2, 3           # RSX_VALUE_*: its value kinds
 SCAN_EXCLUSIVE = 2         # RSX_SCAN_EXCLUSIVE: flags bit 1 of rsx_segmented_scan
 SEARCH_RIGHT = 4           # RSX_SEARCH_RIGHT: flags bit 2 of rsx_segmented_search
@@ -53,7 +54,7 @@ SYMBOLS = [
     "rsx_create", "rsx_destroy", "rsx_set_stream", "rsx_get_stream", "rsx_set_option", "rsx_get_geometry", "rsx_resize",
     "rsx_upload", "rsx_fill_pad", "rsx_download", "rsx_pin_host", "rsx_unpin_host", "rsx_pipeline_submit", "rsx_pipeline_wait", "rsx_host_device_pointer",
     "rsx_histogram", "rsx_scan", "rsx_paste", "rsx_reorder", "rsx_sort", "rsx_sync", "rsx_check_status",
-    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_segmented_merge", "rsx_segmented_set_op", "rsx_segmented_histogram", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
+    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_segmented_merge", "rsx_segmented_set_op", "rsx_segmented_histogram", "rsx_segmented_reduce", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
 ]
 
 
@@ -169,6 +170,7 @@ def load_library() -> C.CDLL:
         "rsx_segmented_merge": ([P, P, P, U64, P, P, P, U64, P, U64, C.c_uint32, P, P, P, P], I),
         "rsx_segmented_set_op": ([P, P, P, U64, P, P, P, U64, P, U64, C.c_uint32, C.c_uint32, P, P, P, P, P], I),
         "rsx_segmented_histogram": ([P, P, U64, P, U64, P, U64, U64, C.c_uint32, U64, C.c_uint32, P], I),
+        "rsx_segmented_reduce": ([P, P, U64, P, U64, C.c_uint32, C.c_uint32, C.c_uint32, P, P], I),
         "rsx_msd_count": ([P, P, U64, I, I, P], I),
         "rsx_msd_scatter": ([P, P, P, U64, P, P], I),
         "rsx_msd_plan": ([P, P, C.c_uint32, C.c_uint32, I, I, P], I),
@@ -513,6 +515,18 @@ class Engine:
         self._check(self.lib.rsx_segmented_scan(
             self._h, C.c_void_p(d_keys) if d_keys else None, C.c_void_p(d_values), n, C.c_void_p(d_offsets) if d_offsets else None, num_segments,
             SCAN_EXCLUSIVE if exclusive else 0, op, value_kind, C.c_void_p(d_values_out)), "rsx_segmented_scan")
+
+    def segmented_reduce(self, d_values: int | None, n: int, d_offsets: int | None, num_segments: int, op: int, value_kind: int,
+                         d_values_out: int | None, d_index_out: int | None = None) -> None:
+        """op (REDUCE_SUM / MIN / MAX / ARGMIN / ARGMAX) over the values of every segment [off[s], off[s+1]) into d_values_out[s], for
+        every s: dense by segment id.  d_offsets None: ONE segment [0, n).  An empty segment gets the op's identity (index 0xFFFFFFFF).
+        The arg ops need d_index_out (uint32, the FIRST extreme's position in its segment; NaN beats every number) and may leave
+        d_values_out None; the others refuse d_index_out.  Float sums are added in an order fixed by the input alone: equal input, equal
+        bits.  n may exceed the capacity and the engine's sort result is left alone.  Asynchronous on the engine's stream; bad offsets
+        (nothing is written then) are reported by the next sync() / check_status()."""
+        self._check(self.lib.rsx_segmented_reduce(
+            self._h, C.c_void_p(d_values) if d_values else None, n, C.c_void_p(d_offsets) if d_offsets else None, num_segments, 0, op, value_kind,
+            C.c_void_p(d_values_out) if d_values_out else None, C.c_void_p(d_index_out) if d_index_out else None), "rsx_segmented_reduce")
 
     def segmented_search(self, d_sorted: int | None, n: int, d_offsets: int | None, num_segments: int, d_queries: int, num_queries: int,
                          d_query_offsets: int | None, d_index_out: int, right: bool = False) -> None:
@@ -1329,6 +1343,147 @@ def cumsum(x, dim: int = -1):
     offsets = None if rows == 1 else torch.arange(0, rows + 1, device=x.device, dtype=torch.int64) * size
     res = _scan_call("cumsum", None, flat, offsets, "sum", False, flat)
     return res.reshape(xm.shape).movedim(-1, dim)
+
+
+# -- reduce on torch tensors ------------------------------------------------------------------------------------------------------------
+_SEGREDUCE_OPS = {"sum": REDUCE_SUM, "min": REDUCE_MIN, "max": REDUCE_MAX, "mean": REDUCE_SUM, "argmin": REDUCE_ARGMIN, "argmax": REDUCE_ARGMAX}
+
+
+def _segreduce_check(what: str, values, op: str) -> str:
+    if op not in _SEGREDUCE_OPS:
+        raise ValueError(f"{what}: op must be one of 'sum', 'min', 'max', 'mean', 'argmin', 'argmax', not {op!r}")
+    vname = str(values.dtype).replace("torch.", "")
+    if vname not in _VALUE_KINDS:
+        raise TypeError(f"{what}: unsupported value type {values.dtype} (int32, int64, float32 or float64)")
+    if op == "mean" and not vname.startswith("float"):
+        raise TypeError(f"{what}: 'mean' needs float32 or float64 values, not {values.dtype}")
+    if not values.is_cuda:
+        raise ValueError(f"{what}: values must be a device tensor (there is no CPU path)")
+    return vname
+
+
+def _segreduce_call(what: str, values, offsets, nseg: int, op: str, want_values: bool, want_index: bool):
+    """One rsx_segmented_reduce call on a 1-D contiguous device tensor; offsets None: one segment.  Returns (values or None, the uint32
+    indices viewed as int32, i.e. -1 for an empty segment, or None)."""
+    import torch
+    vname = _segreduce_check(what, values, op)
+    n = values.numel()
+    if n > (1 << 31):
+        raise ValueError(f"{what}: at most 2^31 elements (rsx_segmented_reduce's bound)")
+    dev = values.device
+    code = _SEGREDUCE_OPS[op]
+    if want_index and code == REDUCE_MIN:
+        code = REDUCE_ARGMIN
+    elif want_index and code == REDUCE_MAX:
+        code = REDUCE_ARGMAX
+    arg = code >= REDUCE_ARGMIN
+    vout = torch.empty(nseg, dtype=values.dtype, device=dev) if want_values or not arg else None
+    iout = torch.empty(nseg, dtype=torch.int32, device=dev) if arg else None
+    if nseg == 0:
+        return vout, iout
+    off = None
+    if offsets is not None:
+        off = offsets if offsets.is_contiguous() and offsets.data_ptr() % 8 == 0 else offsets.clone(memory_format=torch.contiguous_format)
+    device = dev.index if dev.index is not None else torch.cuda.current_device()
+    eng = _scan_engine(device, torch.cuda.current_stream(dev).cuda_stream, 4)
+    eng.segmented_reduce(values.data_ptr() if n else None, n, None if off is None else off.data_ptr(), nseg, code, _VALUE_KINDS[vname],
+                         None if vout is None else vout.data_ptr(), None if iout is None else iout.data_ptr())
+    eng.check_status()      # reports bad offsets of calls that have already finished; no synchronisation
+    return vout, iout
+
+
+def segmented_reduce(values, offsets, op: str = "sum", return_index: bool = False):
+    """op over every segment [offsets[s], offsets[s+1]) of the 1-D device tensor `values` in ONE engine call (rsx_segmented_reduce): a
+    tensor of shape [S], one entry per segment id, empty segments included (0 for 'sum', the dtype's largest / smallest value or +inf /
+    -inf for 'min' / 'max', NaN for 'mean').  ops: 'sum', 'min', 'max', 'mean' (sum / length on the device, float dtypes only), 'argmin',
+    'argmax' (int64 positions inside the segment of the FIRST extreme, -1 for an empty segment; a NaN beats every number, as in torch).
+    return_index=True, for 'min' and 'max', returns (values, indices).  Values: int32, int64, float32, float64; integer sums keep their
+    dtype and wrap; float min / max give NaN if the segment holds one.  Float sums are added in an order fixed by the input alone: the same
+    call gives the same bits every time.  Never synchronises with the host; bad offsets (nothing is written then) raise RadixSortError at
+    a later call or synchronisation of the engine."""
+    import torch
+    _segreduce_check("segmented_reduce", values, op)
+    if return_index and op not in ("min", "max"):
+        raise ValueError("segmented_reduce: return_index goes with op 'min' or 'max'")
+    if values.dim() != 1:
+        raise ValueError("segmented_reduce: values must be 1-D")
+    if offsets is None or offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.device != values.device:
+        raise ValueError("segmented_reduce: offsets must be a 1-D int64 tensor on the values' device")
+    nseg = max(offsets.numel() - 1, 0)
+    v_in = values if values.is_contiguous() else values.contiguous()
+    arg = op in ("argmin", "argmax")
+    vout, iout = _segreduce_call("segmented_reduce", v_in, offsets, nseg, op, not arg, return_index)
+    if op == "mean":
+        return vout / (offsets[1:] - offsets[:-1]).to(vout.dtype)               # (0 / 0 = NaN for an empty segment)
+    if arg:
+        return iout.to(torch.int64)
+    return (vout, iout.to(torch.int64)) if return_index else vout
+
+
+def _reduce_along(what: str, x, op: str, dim: int, keepdim: bool, want_values: bool, want_index: bool):
+    import torch
+    _segreduce_check(what, x, op)
+    if x.dim() == 0:
+        raise ValueError(f"{what}: x must have at least one dimension")
+    dim = dim % x.dim()
+    size = x.shape[dim]
+    if size == 0 and op not in ("sum", "mean"):
+        raise ValueError(f"{what}: '{op}' over an empty dimension has no result")
+    xm = x.movedim(dim, -1)
+    shape = tuple(xm.shape[:-1])
+    rows = 1
+    for d in shape:
+        rows *= d
+    flat = xm.contiguous().reshape(-1)                                          # (a non-contiguous input is copied, as topk does)
+    offsets = None if rows == 1 else torch.arange(0, rows + 1, device=x.device, dtype=torch.int64) * size
+    vout, iout = _segreduce_call(what, flat, offsets, rows, op, want_values, want_index)
+
+    def shaped(t):
+        t = t.reshape(shape)
+        return t.unsqueeze(dim) if keepdim else t
+
+    if vout is not None and op == "mean":
+        vout = vout / size
+    return (None if vout is None else shaped(vout)), (None if iout is None else shaped(iout.to(torch.int64)))
+
+
+def reduce_rows(x, op: str = "sum", dim: int = -1, keepdim: bool = False):
+    """op ('sum', 'min', 'max', 'mean', 'argmin', 'argmax') along `dim` of a device tensor: the rows along `dim` are the segments of ONE
+    rsx_segmented_reduce call.  The result has x's shape without `dim` (kept with size 1 if keepdim).  int32 sums stay int32 and wrap,
+    as cumsum's do; dtypes and reproducibility as segmented_reduce."""
+    arg = op in ("argmin", "argmax")
+    vout, iout = _reduce_along("reduce_rows", x, op, dim, keepdim, not arg, False)
+    return iout if arg else vout
+
+
+def amax(x, dim: int = -1, keepdim: bool = False):
+    """torch.amax(x, dim) on a device tensor, the rows in one call (reduce_rows)."""
+    return _reduce_along("amax", x, "max", dim, keepdim, True, False)[0]
+
+
+def amin(x, dim: int = -1, keepdim: bool = False):
+    """torch.amin(x, dim) on a device tensor, the rows in one call (reduce_rows)."""
+    return _reduce_along("amin", x, "min", dim, keepdim, True, False)[0]
+
+
+def argmax(x, dim: int = -1, keepdim: bool = False):
+    """torch.argmax(x, dim) on a device tensor: the first maximum of every row, a NaN beating every number."""
+    return _reduce_along("argmax", x, "argmax", dim, keepdim, False, False)[1]
+
+
+def argmin(x, dim: int = -1, keepdim: bool = False):
+    """torch.argmin(x, dim) on a device tensor: the first minimum of every row, a NaN beating every number."""
+    return _reduce_along("argmin", x, "argmin", dim, keepdim, False, False)[1]
+
+
+def max_rows(x, dim: int = -1, keepdim: bool = False):
+    """(values, indices) like torch.max(x, dim), in one call; the index is the FIRST maximum's."""
+    return _reduce_along("max_rows", x, "max", dim, keepdim, True, True)
+
+
+def min_rows(x, dim: int = -1, keepdim: bool = False):
+    """(values, indices) like torch.min(x, dim), in one call; the index is the FIRST minimum's."""
+    return _reduce_along("min_rows", x, "min", dim, keepdim, True, True)
 
 
 # -- search on torch tensors ------------------------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@
 #include "rsx_unique.hpp"
 #include "rsx_reduce.hpp"
 #include "rsx_scan_by_key.hpp"
+#include "rsx_segreduce.hpp"
 #include "rsx_search.hpp"
 #include "rsx_compact.hpp"
 #include "rsx_merge.hpp"
@@ -1255,6 +1256,7 @@ int sort_chain(rsx_engine* e, const SortJob& job)
 constexpr uint32_t kStatusCallMerge = 1;         // word 1 of the mapped status words: written by the call that reports, beside its segment in word 0
 constexpr uint32_t kStatusCallSetop = 2;
 constexpr uint32_t kStatusCallHistogram = 3;
+constexpr uint32_t kStatusCallReduce = 4;
 int check_scan_timeout(rsx_engine* e, int status)
 {
     if (e->seg_status_host) {
@@ -1276,6 +1278,9 @@ int check_scan_timeout(rsx_engine* e, int status)
             if (call == kStatusCallHistogram)
                 return fail(status, ("rsx_segmented_histogram: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; every counter of "
                                      "d_counts_out is zero (the first such segment of the call; reported once; the engine remains usable)").c_str());
+            if (call == kStatusCallReduce)
+                return fail(status, ("rsx_segmented_reduce: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; nothing was written (the "
+                                     "first such segment of the call; reported once; the engine remains usable)").c_str());
             return fail(status, ("rsx_segmented_sort / rsx_segmented_topk / rsx_segmented_select: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; it was neither read nor "
                                  "written (the first such segment of the call; reported once; the engine remains usable)").c_str());
         }
@@ -2404,6 +2409,7 @@ int rsx_peer_enable(rsx_engine* e, int peer_device)
 #include "capi_merge.inc"
 #include "capi_setop.inc"
 #include "capi_histogram.inc"
+#include "capi_segreduce.inc"
 
 int rsx_key_range(rsx_engine* e, const void* d_keys, uint64_t n, uint64_t* lo, uint64_t* hi)
 {

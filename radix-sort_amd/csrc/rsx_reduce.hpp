@@ -24,6 +24,7 @@
 
 #include "rsx_unique.hpp"
 
+#include <limits>
 #include <type_traits>
 
 namespace rsx {
@@ -45,6 +46,17 @@ __device__ __forceinline__ Val red_apply(uint32_t op, Val a, Val b)
         const Val lo = (b < a || b != b) ? b : a;
         const Val hi = (b > a || b != b) ? b : a;
         return op == kRedSum ? s : op == kRedMin ? lo : hi;
+    }
+}
+
+// the op's identity: what a restart holds in an exclusive scan (rsx_scan_by_key.hpp) and what an empty segment reduces to (rsx_segreduce.hpp)
+template <typename Val>
+__device__ __forceinline__ Val red_identity(uint32_t op)
+{
+    if constexpr (std::is_integral<Val>::value) {
+        return op == kRedSum ? Val{0} : op == kRedMin ? std::numeric_limits<Val>::max() : std::numeric_limits<Val>::lowest();
+    } else {
+        return op == kRedSum ? Val{0} : op == kRedMin ? std::numeric_limits<Val>::infinity() : -std::numeric_limits<Val>::infinity();
     }
 }
 

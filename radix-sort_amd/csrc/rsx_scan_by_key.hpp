@@ -44,17 +44,6 @@ constexpr uint32_t kScanExclusive = 2u;                           // RSX_SCAN_EX
 constexpr uint32_t kScanRestart = 1u, kScanLive = 2u;             // flags[t]
 constexpr int kScanCarryThreads = 1024;
 
-// what a restart holds in an exclusive scan
-template <typename Val>
-__device__ __forceinline__ Val scan_identity(uint32_t op)
-{
-    if constexpr (std::is_integral<Val>::value) {
-        return op == kRedSum ? Val{0} : op == kRedMin ? std::numeric_limits<Val>::max() : std::numeric_limits<Val>::lowest();
-    } else {
-        return op == kRedSum ? Val{0} : op == kRedMin ? std::numeric_limits<Val>::infinity() : -std::numeric_limits<Val>::infinity();
-    }
-}
-
 template <typename Val>
 struct ScanShared {
     Val wval[kUniqThreads / kWave];
@@ -65,9 +54,17 @@ struct ScanShared {
 // segment starts count: the same walk over the offsets that fall into the tile (s0 = first s with off[s] >= tile_start), without a key
 // being read; without offsets either, the one restart is element 0.  Two barriers unless there are neither keys nor offsets; sh is
 // rewritten by the next call, which the caller separates from this one's readers by a barrier of its own.
-template <typename Key, bool KEYS>
+// ids (rsx_segreduce.hpp, without keys only): the walk also notes which segment ENDS at each element of the tile, for the segments that
+// began in the tile, and which one began in it and goes on behind it.
+struct ScanSegIds {
+    uint32_t last[kUniqTileKeys];                                  // last[x] = s: element x is the last of segment s (written where that holds only)
+    uint32_t open;                                                 // the segment that began in the tile and ends behind it, or 0xFFFFFFFF
+};
+
+template <typename Key, bool KEYS, bool IDS = false>
 __device__ __forceinline__ uint32_t scan_tile_restarts(const Key* __restrict__ keys, uint64_t n, const uint64_t* __restrict__ off, uint64_t nseg,
-                                                       uint64_t lo, uint64_t hi, uint64_t tile_start, uint64_t s0, UniqShared& sh, uint64_t& s0_next)
+                                                       uint64_t lo, uint64_t hi, uint64_t tile_start, uint64_t s0, UniqShared& sh, uint64_t& s0_next,
+                                                       ScanSegIds* ids = nullptr)
 {
     if constexpr (KEYS) {
         Key k[kUniqKpt];
@@ -78,6 +75,14 @@ __device__ __forceinline__ uint32_t scan_tile_restarts(const Key* __restrict__ k
         const uint32_t tid = threadIdx.x;
         if (!off) {                                               // (uniform) one segment [0, n)
             s0_next = s0;
+            if constexpr (IDS) {                                  // (the caller's barrier comes before anybody reads these)
+                if (tid == 0) {
+                    ids->open = tile_start == 0 && n > kUniqTileKeys ? 0u : 0xFFFFFFFFu;
+                    if (tile_start == 0 && n <= kUniqTileKeys && n > 0) {
+                        ids->last[n - 1] = 0u;
+                    }
+                }
+            }
             return tile_start == 0 && tid == 0 ? 1u : 0u;
         }
         if (tid < kUniqTileKeys / 32) {
@@ -85,6 +90,9 @@ __device__ __forceinline__ uint32_t scan_tile_restarts(const Key* __restrict__ k
         }
         if (tid == 0) {
             sh.next_s0 = static_cast<uint32_t>(nseg + 1);
+            if constexpr (IDS) {
+                ids->open = 0xFFFFFFFFu;
+            }
         }
         __syncthreads();
         const uint64_t tile_end = tile_start + kUniqTileKeys;
@@ -97,6 +105,14 @@ __device__ __forceinline__ uint32_t scan_tile_restarts(const Key* __restrict__ k
             if (s < nseg && off[s + 1] > o) {                     // a non-empty segment starts here
                 const uint32_t x = static_cast<uint32_t>(o - tile_start);
                 atomicOr(&sh.segbits[x >> 5], 1u << (x & 31u));
+                if constexpr (IDS) {
+                    const uint64_t e = off[s + 1];
+                    if (e <= tile_end) {
+                        ids->last[static_cast<uint32_t>(e - 1 - tile_start)] = static_cast<uint32_t>(s);
+                    } else {
+                        ids->open = static_cast<uint32_t>(s);     // (one segment at most)
+                    }
+                }
             }
         }
         __syncthreads();
@@ -132,8 +148,9 @@ __device__ __forceinline__ void scan_load_values(const Val* values, uint64_t fir
 // The tile level.  In: acc = the thread's fold from its last restart on (all 16 without one), f = it has a restart.  Out: (x, xf) = T(tid)
 // and whether a restart of the tile lies at or before the thread's end; (ex, exf) = the same for the thread before (tid 0: exf = 0 and ex
 // is not to be used).  One barrier; ss is rewritten by the next call, after the caller's own barrier.
-template <typename Val>
-__device__ __forceinline__ void scan_tile_threads(uint32_t op, Val acc, uint32_t f, ScanShared<Val>& ss, Val& x, uint32_t& xf, Val& ex, uint32_t& exf)
+// apply(a, b) is a o b with a the earlier side: the scan's red_apply, or rsx_segreduce.hpp's fold of (value, position) pairs.
+template <typename Val, typename Apply>
+__device__ __forceinline__ void scan_tile_threads_with(Apply apply, Val acc, uint32_t f, ScanShared<Val>& ss, Val& x, uint32_t& xf, Val& ex, uint32_t& exf)
 {
     const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
     x = acc;
@@ -143,7 +160,7 @@ __device__ __forceinline__ void scan_tile_threads(uint32_t op, Val acc, uint32_t
         const Val y = red_shfl_up(x, d);
         const uint32_t yf = __shfl_up(xf, d);
         if (lane >= static_cast<uint32_t>(d)) {
-            x = xf ? x : red_apply(op, y, x);
+            x = xf ? x : apply(y, x);
             xf |= yf;
         }
     }
@@ -165,7 +182,7 @@ __device__ __forceinline__ void scan_tile_threads(uint32_t op, Val acc, uint32_t
             if (w < wave) {
                 const uint32_t tf = ss.wflag[w];
                 const Val tv = ss.wval[w];
-                pv = tf ? tv : red_apply(op, pv, tv);
+                pv = tf ? tv : apply(pv, tv);
                 pf |= tf;
             }
         }
@@ -173,12 +190,18 @@ __device__ __forceinline__ void scan_tile_threads(uint32_t op, Val acc, uint32_t
             ex = pv;
             exf = pf;
         } else {
-            ex = exf ? ex : red_apply(op, pv, ex);
+            ex = exf ? ex : apply(pv, ex);
             exf |= pf;
         }
-        x = xf ? x : red_apply(op, pv, x);
+        x = xf ? x : apply(pv, x);
         xf |= pf;
     }
+}
+
+template <typename Val>
+__device__ __forceinline__ void scan_tile_threads(uint32_t op, Val acc, uint32_t f, ScanShared<Val>& ss, Val& x, uint32_t& xf, Val& ex, uint32_t& exf)
+{
+    scan_tile_threads_with([op](Val a, Val b) { return red_apply(op, a, b); }, acc, f, ss, x, xf, ex, exf);
 }
 
 // Workgroup b takes the tiles [b * chunk, (b + 1) * chunk); tiles outside [off[0], off[S]) are neither read nor given partials.
@@ -307,7 +330,7 @@ __global__ __launch_bounds__(kUniqThreads) void scan_tile_kernel(const Key* __re
     uint64_t s0 = KEYS || off ? uniq_lower_bound(off, nseg, n, static_cast<uint64_t>(t0) << kUniqTileShift) : 0;
     const bool in_ok = (reinterpret_cast<uintptr_t>(values) & 15u) == 0, out_ok = (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
     const bool exclusive = (scan_flags & kScanExclusive) != 0;
-    const Val id = scan_identity<Val>(op);
+    const Val id = red_identity<Val>(op);
 #pragma unroll 1
     for (uint32_t t = t0; t < t1; ++t) {
         const uint64_t tile_start = static_cast<uint64_t>(t) << kUniqTileShift;
