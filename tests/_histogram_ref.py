@@ -10,11 +10,12 @@ the key's dtype and rounded once.  A descending engine numbers the even forms' b
   bins_of            vectorised (numpy searchsorted / numpy arithmetic in the key's dtype); NO_BIN for a dropped key
   bins_loop          one key at a time, with Python integers and a linear walk of the edges
   histogram_oracle   S x B counts from bins_of; histogram_loop the same from bins_loop
-  piece_paths        [(tile, segment, length, path)] for a layout
+  piece_paths        [(tile, segment, length, path)] for a layout; piece_slots adds the LDS slot a piece gets in a tile of several pieces
+The cases of the bin arithmetic (edges_cases, even_int_cases, even_float_cases) are drawn here once for the CPU selftest and the GPU tests.
 """
 import numpy as np
 
-from _search_ref import UINT, order_map
+from _search_ref import UINT, order_map, order_unmap
 
 NO_BIN = 0xFFFFFFFF
 TILE = 4096
@@ -155,6 +156,20 @@ def piece_paths(n, off, B, cus=256):
     return out
 
 
+def piece_slots(n, off, B, cus=256):
+    """[(tile, segment, length, path, slot)]: piece_paths with the slot of sh.piece_seg that an LDS piece is numbered by, (piece start -
+    tile start) >> 8, in a tile of several pieces; None for a direct piece and for the one piece of a tile inside one segment (that
+    branch has no slots)"""
+    paths = piece_paths(n, off, B, cus)
+    o = _offsets(n, off)
+    per_tile = np.bincount([p[0] for p in paths], minlength=1)
+    out = []
+    for t, s, L, path in paths:
+        start = max(int(o[s]), t * TILE)
+        out.append((t, s, L, path, None if path == "direct" or per_tile[t] == 1 else (start - t * TILE) // DIRECT_PIECE))
+    return out
+
+
 def lds_layout(B):
     """'wave_private' or 'shared' or 'none': the counters of the LDS path for B bins"""
     return "none" if B > LDS_MAX else "wave_private" if B <= WAVE_PRIVATE_MAX else "shared"
@@ -278,3 +293,152 @@ LAYOUTS = {
     "empties": (empties_layout, 16, {"lds_first", "lds_flush"}),
     "fifties": (fifties_layout, 16, {"direct"}),
 }
+
+
+# -- the cases of the bin arithmetic: tests/test_histogram.py sends them through host/bin/bins_selftest (g++), ------------------------------
+# -- tests/test_gpu_histogram_paths.py through the kernels; both draw them here, from the same seeds ------------------------------------------
+
+def around(dt, values):
+    """every value, the key before and the key after it in ascending order"""
+    v = order_map(np.array(values, dtype=dt))
+    one = v.dtype.type(1)
+    return np.concatenate([order_unmap(v - one, dt), order_unmap(v, dt), order_unmap(v + one, dt)])
+
+
+def edges_cases(dt, descending):
+    """(B, edges, keys): every edge and the keys next to it, random keys, the float specials; B = 13 has -0.0 and +0.0 as two edges"""
+    dt = np.dtype(dt)
+    rng = np.random.default_rng(80 + DTYPES.index(dt.name) * 2 + descending)
+    for B in (1, 2, 13, 4096):
+        edges = sorted_edges(rng, dt, B, SPAN if B < 4096 else None, descending)
+        if dt.kind == "f" and B == 13:                              # -0.0 next to +0.0 as two edges
+            edges[:2] = [0.0, -0.0]
+            edges = edges[np.argsort(order_map(edges, descending), kind="stable")]
+            assert np.unique(edges.view(UINT[dt.itemsize])).size == B + 1
+        keys = np.concatenate([around(dt, edges), random_keys(rng, dt, 500, SPAN)] + ([special_floats(dt)] if dt.kind == "f" else []))
+        yield B, edges, keys
+
+
+def even_int_cases(dt, descending):
+    """(shift, lo, B, keys): lo at info.min and at info.max - 70, width_shift up to width - 1; the keys around every bin boundary"""
+    dt = np.dtype(dt)
+    rng = np.random.default_rng(90 + DTYPES.index(dt.name) * 2 + descending)
+    info = np.iinfo(dt)
+    width = 8 * dt.itemsize
+    for shift in (0, 5, width - 1):
+        for lo in ([0, 1000, info.max - 70] if dt.kind == "u" else [-1000, -1, 0, info.min, info.max - 70]):
+            for B in (1, 3, 64):
+                edge = [lo + (b << shift) for b in range(B + 2) if lo + (b << shift) <= info.max]
+                keys = np.concatenate([around(dt, edge), around(dt, [info.min, info.max, 0]), random_keys(rng, dt, 200, None),
+                                       random_keys(rng, dt, 200, 2000)])
+                yield shift, lo, B, keys
+
+
+def even_float_cases(dt, descending):
+    """(B, lo, hi, keys): keys whose product (x - lo) * scale lies one ulp either side of an integer: x = lo + b / scale and its
+    neighbours, twice over; lo and hi and theirs; the specials.  A subnormal x - lo is unspecified: no key has one."""
+    dt = np.dtype(dt)
+    rng = np.random.default_rng(95 + DTYPES.index(dt.name) * 2 + descending)
+    for B, lo, hi in ((1, -1.0, 1.0), (7, -3.0, 11.0), (64, 0.0, 64.0), (100, 0.1, 0.7), (4096, -1024.0, 1536.0), (50257, 1.0, 3.0)):
+        lo_, hi_ = dt.type(lo), dt.type(hi)
+        scale = dt.type(dt.type(B) / dt.type(hi_ - lo_))
+        b = np.unique(rng.integers(0, B + 1, 40))
+        near = (lo_ + (b.astype(dt) / scale).astype(dt)).astype(dt)
+        keys = np.concatenate([around(dt, around(dt, near)), around(dt, [lo_, hi_]), special_floats(dt),
+                               (rng.standard_normal(300) * (hi - lo)).astype(dt) + lo_])
+        sub = np.abs((keys - lo_).astype(dt))
+        keys = keys[~((sub > 0) & (sub < np.finfo(dt).tiny))]       # a subnormal x - lo is unspecified: no test rests on it
+        yield B, lo, hi, keys
+
+
+def even_float_case_holds(keys, B, lo, hi, want, descending):
+    """what a float case must hold, from the referee's bins `want` alone: products that are whole numbers and products that are not,
+    dropped keys, lo in the first bin and hi in the last"""
+    dt = keys.dtype
+    lo_, hi_ = dt.type(lo), dt.type(hi)
+    scale = dt.type(dt.type(B) / dt.type(hi_ - lo_))
+    t = ((keys - lo_).astype(dt) * scale).astype(dt)
+    inside = want != NO_BIN
+    assert np.any(inside & (t != np.floor(t))) and np.any(inside & (t == np.floor(t))) and np.any(~inside)
+    top = B - 1 if not descending else 0
+    assert want[np.flatnonzero(keys == hi_)[0]] == top and want[np.flatnonzero(keys == lo_)[0]] == B - 1 - top
+
+
+# How the GPU test sends one case (its keys once, in this order): [(name, n, off)] with the keys repeated up to n.
+ARITH_MIN_KEYS = 2 * DIRECT_PIECE + 100            # both halves of the two-segment form are LDS pieces
+
+
+def arith_forms(nkeys):
+    """one segment (LDS up to 4096 bins); two segments cut at an odd position; pieces of 255 keys (all direct)"""
+    n = max(nkeys, ARITH_MIN_KEYS)
+    cut = (n // 2) | 1
+    return [("one segment", n, None), ("two segments", n, np.array([0, cut, n], dtype=np.uint64)),
+            ("pieces of 255", n, np.minimum(np.arange(0, n + 255, 255, dtype=np.uint64), np.uint64(n)))]
+
+
+# -- the piece-slot layouts: every one at most 3 tiles (one tile a workgroup) -----------------------------------------------------------------
+
+def slots16_layout():
+    """(n, off): 16 segments of exactly 256 keys on the tile's grid: slots 0 .. 15 of one tile"""
+    return TILE, np.arange(17, dtype=np.uint64) * np.uint64(DIRECT_PIECE)
+
+
+def slots16_shifted_layout():
+    """(n, off): a 255-key segment, then 17 of 256 keys: piece starts 255 + 256 i; the one from 4095 has one key in tile 0 and 255 in tile 1"""
+    off = np.concatenate([[0], 255 + DIRECT_PIECE * np.arange(18)]).astype(np.uint64)
+    return int(off[-1]) + 5, off
+
+
+def lengths_cycle_layout():
+    """(n, off): lengths 255, 256, 257, 256 eight times: two tiles, every piece a whole segment"""
+    return 2 * TILE, offsets_from([255, 256, 257, 256] * 8)
+
+
+def ends_with_tile_layout():
+    """(n, off): tile 0 ends with an LDS piece of a segment that ends with the tile; tile 1 lies inside the next segment, which goes on into tile 2"""
+    return 3 * TILE, np.array([5, 3000, TILE, 9000, 3 * TILE - 7], dtype=np.uint64)
+
+
+SLOT_LAYOUTS = {"slots16": slots16_layout, "slots16_shifted": slots16_shifted_layout, "lengths_cycle": lengths_cycle_layout,
+                "ends_with_tile": ends_with_tile_layout}
+
+
+def shifted_bins(rng, n, off, B):
+    """the bin of every key, as numbers: segment s holds bins (s + {0, 1, 2}) % B, so that neighbours' histograms differ; one key in 50
+    has bin B + 1 (dropped); outside the segments anything in [0, B + 2)"""
+    o = _offsets(n, off)
+    seg = np.repeat(np.arange(o.size - 1, dtype=np.int64), np.diff(o))
+    b = rng.integers(0, B + 2, n)
+    live = (seg + rng.integers(0, 3, seg.size)) % B
+    b[int(o[0]):int(o[-1])] = np.where(rng.integers(0, 50, seg.size) == 0, B + 1, live)
+    return b
+
+
+SLOT_EDGE_STEP = 1 << 40                           # the uint64 edges of the B = 4096 form: step * arange(B + 1); a key of bin b is b * step + step / 2
+
+
+# -- the counter layout boundary and the zero fill ------------------------------------------------------------------------------------------------
+
+BOUNDARY_BINS = [1023, 1024, 1025, 4095]           # the last wave-private size, cnt[4096] filled exactly by four copies, the first shared size; the last-but-one
+ZERO_SMALL = {1: (1, 1), 2: (2, 1), 3: (3, 1), 4: (2, 2), 5: (1, 5), 7: (7, 1), 8: (2, 4), 9: (3, 3)}      # S * B -> (S, B)
+ZERO_ALIGN = [0, 4, 8, 12]                         # bytes from a 16-byte boundary to the first counter
+ZERO_BIG_BINS = 65
+
+
+def zero_small_layout(S):
+    """(n, off): S segments of 0, 1, 2, 0, 1, 2 ... keys from position 1, one trailing key"""
+    off = offsets_from([s % 3 for s in range(S)], start=1)
+    return int(off[-1]) + 1, off
+
+
+def zero_big_layout():
+    """(n, off): fifties_layout plus one segment: 2^16 + 1 segments of 50 keys"""
+    S = (1 << 16) + 1
+    return 50 * S, (np.arange(S + 1, dtype=np.uint64) * np.uint64(50))
+
+
+def zero_grid(total, cus=256):
+    """(workgroups of bins_zero_kernel, 16-byte stores at most, trips of the grid-stride loop) for `total` counters"""
+    nvec = total // 4
+    grid = min((nvec + 255) // 256 + 1, 16 * cus)
+    return grid, nvec, (nvec + grid * 256 - 1) // (grid * 256)

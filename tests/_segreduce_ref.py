@@ -6,7 +6,10 @@ reduce_oracle   op over every segment, one slice at a time.  Integer sums wrap; 
 model_sum       the association written at the top of rsx_segreduce.hpp, transcribed for float32 / float64 from the values, the offsets
                 and n alone: the bits the kernels must produce.
 reduce_terms    per segment: the elements folded and the sum of their magnitudes, for the any-order error bound.
-The named layouts at the end are (n, offsets) pairs; paths() says, from a layout alone, which paths of the kernels it reaches.
+reduce_fast, terms_fast   the same two by ufunc.reduceat, without a Python loop over the segments (tests/test_segreduce.py holds them
+                to the loop forms).
+The named layouts at the end are (n, offsets) pairs; paths() says, from a layout alone, which paths of the kernels it reaches, and
+join_schedule() which open tiles every workgroup of the join takes, in order.
 """
 import numpy as np
 
@@ -79,6 +82,59 @@ def reduce_terms(values, off=None):
     o = _offsets(v.size, off)
     wide = WIDE[v.dtype]
     mag = np.array([np.abs(v[o[s]:o[s + 1]].astype(wide)).sum() for s in range(len(o) - 1)], dtype=wide)
+    return (o[1:] - o[:-1]).astype(np.int64), mag
+
+
+# -- the same without a loop over the segments, for layouts of a million of them ----------------------------------------------------------
+
+def _live(o):
+    """the non-empty segments and where each starts inside [off[0], off[S]): they lie back to back there, which is what reduceat folds"""
+    live = np.flatnonzero(o[1:] > o[:-1])
+    return live, o[live] - o[0]
+
+
+def reduce_fast(values, off=None, op="sum"):
+    """reduce_oracle by ufunc.reduceat over the non-empty segments.  The float sums are folded left to right in the wide format where
+    reduce_oracle adds pairwise: equal wherever the wide sums are exact, one rounding of the wide format apart otherwise.  The sign of a
+    zero minimum or maximum is numpy's choice in both forms (the arg ops return the element itself: its own bits)."""
+    v = np.asarray(values)
+    o = _offsets(v.size, off)
+    nseg = len(o) - 1
+    arg = op in ("argmin", "argmax")
+    low = op in ("min", "argmin")
+    floats = v.dtype.kind == "f"
+    res = np.zeros(nseg, dtype=WIDE[v.dtype]) if op == "sum" and floats else np.full(nseg, identity(v.dtype, op), dtype=v.dtype)
+    idx = np.full(nseg, -1, dtype=np.int64) if arg else None
+    live, at = _live(o)
+    if live.size == 0:
+        return res, idx
+    x = v[o[0]:o[-1]]
+    with np.errstate(over="ignore", invalid="ignore"):
+        if op == "sum":
+            res[live] = np.add.reduceat(x.astype(res.dtype), at) if floats else np.add.reduceat(x, at, dtype=v.dtype)
+            return res, idx
+        best = (np.minimum if low else np.maximum).reduceat(x, at)             # (NaN if the segment holds one)
+        if not arg:
+            res[live] = best
+            return res, idx
+        lengths = (o[live + 1] - o[live]).astype(np.int64)
+        mine = np.repeat(best, lengths)
+        hit = np.flatnonzero((x == mine) | ((x != x) & (mine != mine)))     # a NaN beats every number: where the extreme is NaN the NaNs are the hits
+        first = hit[np.searchsorted(hit, at, side="left")]                  # the first hit at or behind each start: inside the segment, which has one
+        idx[live] = first - at
+        res[live] = x[first]
+    return res, idx
+
+
+def terms_fast(values, off=None):
+    """reduce_terms by reduceat (the magnitudes folded left to right in the wide format)"""
+    v = np.asarray(values)
+    o = _offsets(v.size, off)
+    wide = WIDE[v.dtype]
+    mag = np.zeros(len(o) - 1, dtype=wide)
+    live, at = _live(o)
+    if live.size:
+        mag[live] = np.add.reduceat(np.abs(v[o[0]:o[-1]].astype(wide)), at)
     return (o[1:] - o[:-1]).astype(np.int64), mag
 
 
@@ -226,6 +282,133 @@ def layout_all_empty():
     return 5000, offsets_from([0] * 7, start=4100)
 
 
+def dense_cycle(lengths, lead=()):
+    """(n, off): off[0] = 3, then `lead`, then `lengths` over and over, cut so that the segments cover two tiles and 37 elements; 5 trailing elements"""
+    want = 2 * TILE + 37
+    out = list(lead)
+    while sum(out) < want:
+        out += list(lengths)
+    total = np.cumsum(out)
+    keep = int(np.searchsorted(total, want, side="left")) + 1
+    out = out[:keep]
+    out[-1] -= int(total[keep - 1]) - want
+    off = offsets_from(out, start=3)
+    assert int(off[-1]) == 3 + want
+    return int(off[-1]) + 5, off
+
+
+def layout_every_element():
+    """every element is a segment of its own: 16 flags in every thread, 4096 entries of ids.last in a whole tile"""
+    return dense_cycle([1])
+
+
+def layout_ones_and_empties():
+    """lengths 1, 0, 2, 0, 0, 1, 3: empty segments before and behind one-element segments, four starts in many a thread"""
+    return dense_cycle([1, 0, 2, 0, 0, 1, 3])
+
+
+def layout_thread_edges():
+    """lengths 16, 1, 15 from position 16 on (a first segment of 13 elements takes off[0] = 3 there): boundaries on every thread edge
+    and, every other thread, one element behind it"""
+    return dense_cycle([16, 1, 15], lead=[13])
+
+
+DENSE = {"every element": layout_every_element, "ones and empties": layout_ones_and_empties, "thread edges": layout_thread_edges}
+
+POSITIONS = [0, 1, 15, 16, 17, 1023, 1024, 4095, 4096, 4097, 8191, 8192, 12287, 12288]
+POSITIONS_N = 3 * TILE
+
+
+def position_layouts():
+    """[(n, off)]: one segment [lo, hi) for every pair lo < hi of POSITIONS, n = 3 tiles; then the two segments [3, b) and [b, n - 3) for
+    every b of POSITIONS that leaves both non-empty (0, 1, 12287 and 12288 would make the offsets decrease: no valid call); and two
+    segments that end on a thread edge inside a LATER tile than they began in, which no pair of POSITIONS does"""
+    n = POSITIONS_N
+    one = [(n, np.array([a, b], dtype=np.uint64)) for i, a in enumerate(POSITIONS) for b in POSITIONS[i + 1:]]
+    two = [(n, np.array([3, b, n - 3], dtype=np.uint64)) for b in POSITIONS if 3 < b < n - 3]
+    later = [(n, np.array([5, TILE + 1024], dtype=np.uint64)), (n, np.array([5, 2 * TILE + 16], dtype=np.uint64))]
+    return one + two + later
+
+
+def layout_two_joins():
+    """4401 tiles, 9 boundaries: on 256 CUs the join's grid is 4096 workgroups, and workgroups 5, 105 and 125 take a second open tile"""
+    T = TILE
+    n = 4400 * T + 7
+    return n, np.array([11, 5 * T + 100, 35 * T + 50, 105 * T + 7, 300 * T + 9, 4101 * T + 3, 4201 * T + 1, 4221 * T + 2, n - 3], dtype=np.uint64)
+
+
+def layout_million_segments():
+    """2^20 + 4099 segments, lengths 1, 0, 2, 0, 0, 1 over and over from off[0] = 5; 5 trailing elements"""
+    S = (1 << 20) + 4099
+    off = offsets_from(np.resize(np.array([1, 0, 2, 0, 0, 1], dtype=np.int64), S), start=5)
+    return int(off[-1]) + 5, off
+
+
+def chunk_of(n, cus=CUS):
+    """tiles a workgroup of segreduce_tile_kernel walks"""
+    tiles = (n + TILE - 1) // TILE
+    return max((tiles + 16 * cus - 1) // (16 * cus), 1)
+
+
+def join_grid(n, nseg, cus=CUS):
+    """workgroups of segreduce_join_kernel: one thread per segment and one workgroup per tile, at most 16 per CU"""
+    return min(max((nseg + JOIN - 1) // JOIN, (n + TILE - 1) // TILE, 1), 16 * cus)
+
+
+def join_schedule(n, off, cus=CUS):
+    """{workgroup: [(open tile, m)]} in the order the workgroup takes them: tile t is open if a segment that began in it goes on behind
+    it, m = the tiles after t that the segment reaches; the workgroups take the tiles from off[0]'s on, grid-stride"""
+    o = _offsets(n, off)
+    grid = join_grid(n, len(o) - 1, cus)
+    live = np.flatnonzero(o[1:] > o[:-1])
+    t, u = o[live] // TILE, (o[live + 1] - 1) // TILE
+    t_first = int(o[0]) // TILE
+    out = {}
+    for a, b in zip(t[u > t].tolist(), u[u > t].tolist()):
+        out.setdefault((a - t_first) % grid, []).append((a, b - a))
+    return out
+
+
+def dense_paths(o):
+    """how densely the segment starts lie (rsx_segreduce.hpp stores a segment between two flags of one thread at once, by ids.last)"""
+    got = set()
+    lengths = o[1:] - o[:-1]
+    starts = o[:-1][lengths > 0]
+    if starts.size:
+        per_thread = np.bincount(starts // KPT)
+        if per_thread.max() >= 3:
+            got.add("three or more starts in a thread")
+        if per_thread.max() == KPT:
+            got.add("16 starts in a thread")
+        if np.bincount(starts // TILE).max() == TILE:
+            got.add("4096 starts in a tile")
+        if np.any(starts % KPT == 0):
+            got.add("boundary on a thread edge")
+        if np.any(starts % KPT == 1):
+            got.add("boundary one element behind a thread edge")
+    empty = lengths == 0
+    if empty.any() and lengths.size > 2:
+        after_one = empty[1:] & (lengths[:-1] == 1)                # an empty segment right behind a one-element segment,
+        before_one = empty[:-1] & (lengths[1:] == 1)               # and one right before a one-element segment
+        if after_one.any() and before_one.any():
+            got.add("empty between one-element segments")
+    return got
+
+
+def stop_paths(o):
+    """where off[S] stands in its tile: the stop flag of segreduce_tile_kernel"""
+    got = set()
+    lo, hi = int(o[0]), int(o[-1])
+    if lo < hi:
+        if hi % KPT == 0 and hi % TILE != 0:
+            got.add("stop on a thread edge inside a tile")
+        if hi % TILE == 1:
+            got.add("stop at a tile's second element")
+        if hi % TILE == TILE - 1:
+            got.add("stop at a tile's last element")
+    return got
+
+
 def paths(n, off):
     """the paths of rsx_segreduce.hpp that a layout reaches, from the layout alone"""
     o = _offsets(n, off)
@@ -237,6 +420,7 @@ def paths(n, off):
         got.add("off[0] > 0")
     if hi < n:
         got.add("off[S] < n")
+    got |= dense_paths(o) | stop_paths(o)
     for s in range(len(o) - 1):
         b, e = int(o[s]), int(o[s + 1])
         if b == e:

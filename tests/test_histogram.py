@@ -12,8 +12,8 @@ import numpy as np
 import pytest
 
 import _histogram_ref as H
-from _histogram_ref import NO_BIN, bins_of, histogram_loop, histogram_oracle, piece_paths
-from _search_ref import UINT, order_map, order_unmap
+from _histogram_ref import NO_BIN, bins_of, histogram_loop, histogram_oracle, piece_paths, piece_slots
+from _search_ref import UINT
 from test_search import header_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -141,25 +141,12 @@ def selftest_bins(tmp_path, keys, bins, lo=0, hi=0, shift=0, descending=False, e
     return np.array([int(v) for v in proc.stdout.split()], dtype=np.int64)
 
 
-def around(dt, values):
-    """every value, the key before and the key after it in ascending order"""
-    v = order_map(np.array(values, dtype=dt))
-    one = v.dtype.type(1)
-    return np.concatenate([order_unmap(v - one, dt), order_unmap(v, dt), order_unmap(v + one, dt)])
-
+# (the cases are drawn in tests/_histogram_ref.py: tests/test_gpu_histogram_paths.py sends the same keys through the kernels)
 
 @pytest.mark.parametrize("descending", [False, True], ids=["asc", "desc"])
 @pytest.mark.parametrize("dt", H.DTYPES)
 def test_selftest_edges_form(tmp_path, dt, descending):
-    rng = np.random.default_rng(80 + H.DTYPES.index(dt) * 2 + descending)
-    dt = np.dtype(dt)
-    for B in (1, 2, 13, 4096):
-        edges = H.sorted_edges(rng, dt, B, H.SPAN if B < 4096 else None, descending)
-        if dt.kind == "f" and B == 13:                              # -0.0 next to +0.0 as two edges
-            edges[:2] = [0.0, -0.0]
-            edges = edges[np.argsort(order_map(edges, descending), kind="stable")]
-            assert np.unique(edges.view(UINT[dt.itemsize])).size == B + 1
-        keys = np.concatenate([around(dt, edges), H.random_keys(rng, dt, 500, H.SPAN)] + ([H.special_floats(dt)] if dt.kind == "f" else []))
+    for B, edges, keys in H.edges_cases(dt, descending):
         want = bins_of(keys, edges, descending=descending)
         assert np.array_equal(selftest_bins(tmp_path, keys, edges, descending=descending), want), B
         assert np.any(want == NO_BIN) and np.any(want == B - 1) and np.any(want == 0)
@@ -168,43 +155,21 @@ def test_selftest_edges_form(tmp_path, dt, descending):
 @pytest.mark.parametrize("descending", [False, True], ids=["asc", "desc"])
 @pytest.mark.parametrize("dt", ["uint32", "int32", "uint64", "int64"])
 def test_selftest_even_integer_form(tmp_path, dt, descending):
-    rng = np.random.default_rng(90 + H.DTYPES.index(dt) * 2 + descending)
     dt = np.dtype(dt)
-    info = np.iinfo(dt)
-    width = 8 * dt.itemsize
-    for shift in (0, 5, width - 1):
-        for lo in ([0, 1000, info.max - 70] if dt.kind == "u" else [-1000, -1, 0, info.min, info.max - 70]):
-            for B in (1, 3, 64):
-                edge = [lo + (b << shift) for b in range(B + 2) if lo + (b << shift) <= info.max]
-                keys = np.concatenate([around(dt, edge), around(dt, [info.min, info.max, 0]), H.random_keys(rng, dt, 200, None),
-                                       H.random_keys(rng, dt, 200, 2000)])
-                want = bins_of(keys, B, lo=lo, shift=shift, descending=descending)
-                assert np.array_equal(selftest_bins(tmp_path, keys, B, lo=lo, shift=shift, descending=descending), want), (shift, lo, B)
-    selftest_bins(tmp_path, np.zeros(1, dtype=dt), 4, shift=width, expect=2)           # width_shift < 8 * key_bytes
+    for shift, lo, B, keys in H.even_int_cases(dt, descending):
+        want = bins_of(keys, B, lo=lo, shift=shift, descending=descending)
+        assert np.array_equal(selftest_bins(tmp_path, keys, B, lo=lo, shift=shift, descending=descending), want), (shift, lo, B)
+    selftest_bins(tmp_path, np.zeros(1, dtype=dt), 4, shift=8 * dt.itemsize, expect=2)           # width_shift < 8 * key_bytes
 
 
 @pytest.mark.parametrize("descending", [False, True], ids=["asc", "desc"])
 @pytest.mark.parametrize("dt", ["float32", "float64"])
 def test_selftest_even_float_form(tmp_path, dt, descending):
-    rng = np.random.default_rng(95 + H.DTYPES.index(dt) * 2 + descending)
     dt = np.dtype(dt)
-    for B, lo, hi in ((1, -1.0, 1.0), (7, -3.0, 11.0), (64, 0.0, 64.0), (100, 0.1, 0.7), (4096, -1024.0, 1536.0), (50257, 1.0, 3.0)):
-        lo_, hi_ = dt.type(lo), dt.type(hi)
-        scale = dt.type(dt.type(B) / dt.type(hi_ - lo_))
-        # keys whose product (x - lo) * scale lies one ulp either side of an integer: x = lo + b / scale and its neighbours, twice over
-        b = np.unique(rng.integers(0, B + 1, 40))
-        near = (lo_ + (b.astype(dt) / scale).astype(dt)).astype(dt)
-        keys = np.concatenate([around(dt, around(dt, near)), around(dt, [lo_, hi_]), H.special_floats(dt),
-                               (rng.standard_normal(300) * (hi - lo)).astype(dt) + lo_])
-        sub = np.abs((keys - lo_).astype(dt))
-        keys = keys[~((sub > 0) & (sub < np.finfo(dt).tiny))]       # a subnormal x - lo is unspecified: no test rests on it
+    for B, lo, hi, keys in H.even_float_cases(dt, descending):
         want = bins_of(keys, B, lo=lo, hi=hi, descending=descending)
         assert np.array_equal(selftest_bins(tmp_path, keys, B, lo=lo, hi=hi, descending=descending), want), (B, lo, hi)
-        t = ((keys - lo_).astype(dt) * scale).astype(dt)
-        inside = want != NO_BIN
-        assert np.any(inside & (t != np.floor(t))) and np.any(inside & (t == np.floor(t))) and np.any(~inside)
-        top = B - 1 if not descending else 0
-        assert want[np.flatnonzero(keys == hi_)[0]] == top and want[np.flatnonzero(keys == lo_)[0]] == B - 1 - top
+        H.even_float_case_holds(keys, B, lo, hi, want, descending)
     for lo, hi in ((1.0, 1.0), (2.0, 1.0), (0.0, np.inf), (np.nan, 1.0), (-np.finfo(dt).max, np.finfo(dt).max)):
         selftest_bins(tmp_path, np.zeros(1, dtype=dt), 4, lo=lo, hi=hi, expect=2)       # refused: not finite, not lo < hi, no finite scale
 
@@ -256,6 +221,100 @@ def test_matrix_cases_hold_what_they_promise(dt, form):
                 assert np.any(live == np.dtype(dt).type(args["lo"]))
                 if np.dtype(dt).kind == "f":
                     assert np.any(live == np.dtype(dt).type(args["hi"])) and np.any(np.isnan(live)) and np.any(np.isinf(live))
+
+
+# -- the layouts of tests/test_gpu_histogram_paths.py ----------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("dt", H.DTYPES)
+def test_arithmetic_cases_take_the_lds_and_the_direct_path(dt):
+    """every case of the three selftests above, in the three forms the GPU test sends it in: as one segment and as two segments its keys
+    are counted in LDS (but for B = 50257, the direct path by itself), cut into pieces of 255 keys they all go the direct way"""
+    dt = np.dtype(dt)
+    cases = 0
+    for descending in (False, True):
+        sized = [(B, keys.size) for B, _, keys in H.edges_cases(dt, descending)]
+        if dt.kind == "f":
+            sized += [(B, keys.size) for B, _, _, keys in H.even_float_cases(dt, descending)]
+        else:
+            sized += [(B, keys.size) for _, _, B, keys in H.even_int_cases(dt, descending)]
+        for B, size in set(sized):
+            forms = H.arith_forms(size)
+            assert [f[0] for f in forms] == ["one segment", "two segments", "pieces of 255"]
+            for name, n, off in forms:
+                assert n >= size and n > 2 * H.DIRECT_PIECE
+                pieces = piece_paths(n, off, B)
+                assert sum(p[2] for p in pieces) == n
+                if name == "pieces of 255" or B > H.LDS_MAX:
+                    assert {p[3] for p in pieces} == {"direct"} and (name != "pieces of 255" or max(p[2] for p in pieces) == 255)
+                elif name == "one segment":
+                    assert pieces[0][3] == "lds_first" and pieces[0][2] > H.DIRECT_PIECE
+                else:
+                    cut = int(off[1])
+                    assert cut % 2 == 1 and [p[3] for p in pieces if p[0] == cut // H.TILE] == ["lds_first", "lds_flush"]      # both sides of the cut in LDS
+            cases += 1
+        assert {B for B, _ in sized} >= ({1, 2, 13, 4096} | ({50257, 100} if dt.kind == "f" else {3, 64}))
+    assert cases >= 10
+
+
+def test_slot_layouts_reach_every_slot_and_the_direct_boundary():
+    """the four piece-slot layouts, B = 64 and B = 4096: slots 0 .. 15 in one tile; pieces of 255, 256 and 257 keys; an LDS piece that
+    ends with its tile before a tile inside another segment; and neighbouring segments' histograms differ"""
+    rng = np.random.default_rng(2)
+    for B in (64, 4096):
+        got = {}
+        for name, layout in H.SLOT_LAYOUTS.items():
+            n, off = layout()
+            assert (n + H.TILE - 1) // H.TILE <= 3 and H.chunk_of(n) == 1
+            got[name] = piece_slots(n, off, B)
+            o = off.astype(np.int64)
+            assert sum(p[2] for p in got[name]) == int(o[-1] - o[0])
+            assert all((p[4] is not None) == (p[3] != "direct") for p in got[name] if name != "ends_with_tile")
+            counts = np.stack([np.bincount(b[b < B], minlength=B) for b in np.split(H.shifted_bins(rng, n, off, B)[o[0]:o[-1]], np.cumsum(np.diff(o))[:-1])])
+            assert np.all(np.any(counts[1:] != counts[:-1], axis=1)) and counts.sum() < int(o[-1] - o[0])       # neighbours differ; some keys are dropped
+        slots = lambda name, tile: [p[4] for p in got[name] if p[0] == tile and p[4] is not None]
+        assert slots("slots16", 0) == list(range(16))                                  # 15 flushes inside one tile
+        assert {p[2] for p in got["slots16"]} == {256}
+        sh = got["slots16_shifted"]
+        assert sh[0][2:4] == (255, "direct") and slots("slots16_shifted", 0) == list(range(15))
+        assert [p[1:4] for p in sh if p[1] == 16] == [(16, 1, "direct"), (16, 255, "direct")]           # the piece over the tile edge: both parts short
+        assert slots("slots16_shifted", 1) == [0] and sh[-1][2] == 256
+        cyc = got["lengths_cycle"]
+        assert {p[2] for p in cyc} == {255, 256, 257} and all((p[3] == "direct") == (p[2] == 255) for p in cyc)
+        assert slots("lengths_cycle", 0) == slots("lengths_cycle", 1) == [0, 1, 3, 4, 5, 7, 8, 9, 11, 12, 13, 15]
+        end = got["ends_with_tile"]
+        assert [(p[0], p[1], p[4]) for p in end] == [(0, 0, 0), (0, 1, 11), (1, 2, None), (2, 2, 0), (2, 3, 3)]
+        assert end[1][2] == H.TILE - 3000 and all(p[3] != "direct" for p in end)       # the LDS piece of slot 11 ends with tile 0
+    # the layouts from before reach slots {0, 1, 4, 7, 8, 11, 12} only and no piece within one key of the direct boundary
+    old = set()
+    for name, (layout, B, _) in H.LAYOUTS.items():
+        if name.startswith("big") or B > H.LDS_MAX:
+            continue
+        pieces = piece_slots(*layout(), B)
+        old |= {p[4] for p in pieces if p[4] is not None}
+        assert not any(255 <= p[2] <= 257 for p in pieces if name != "ragged_lds")
+    assert 15 not in old
+
+
+def test_boundary_bins_and_zero_fill_sizes():
+    assert [H.lds_layout(B) for B in H.BOUNDARY_BINS] == ["wave_private", "wave_private", "shared", "shared"]
+    assert 4 * 1024 == H.LDS_MAX                                                       # four copies of 1024 counters fill cnt[] exactly
+    # the zero fill: totals below one 16-byte store at every alignment, and one total with a second trip of the grid-stride loop
+    assert sorted(H.ZERO_SMALL) == [1, 2, 3, 4, 5, 7, 8, 9] and all(S * B == total for total, (S, B) in H.ZERO_SMALL.items())
+    for total in H.ZERO_SMALL:
+        for align in H.ZERO_ALIGN:
+            head = min(total, ((16 - align) % 16) // 4)
+            nvec = (total - head) // 4
+            assert nvec <= 2 and total - head - 4 * nvec <= 3
+    assert any(min(t, ((16 - a) % 16) // 4) == t for t in H.ZERO_SMALL for a in H.ZERO_ALIGN)             # head = total: nothing but the head
+    assert any((t - min(t, ((16 - a) % 16) // 4)) // 4 == 0 and t > 3 for t in H.ZERO_SMALL for a in H.ZERO_ALIGN)      # nvec == 0 with a head and a tail
+    n, off = H.zero_big_layout()
+    f_n, f_off = H.fifties_layout()
+    assert len(off) == len(f_off) + 1 and np.array_equal(off[:-1], f_off) and n == f_n + 50
+    total = (len(off) - 1) * H.ZERO_BIG_BINS
+    assert total == 4259905 and total % 2 == 1 and total / 4 > 256 * 16 * 256
+    grid, nvec, trips = H.zero_grid(total)
+    assert grid == 16 * 256 and trips == 2 and H.zero_grid(1 << 20)[2] == 1              # (2^20 counters, the most before: one trip)
+    assert {p[3] for p in piece_paths(n, off, H.ZERO_BIG_BINS)} == {"direct"}
 
 
 # -- no GPU: the call and the helpers raise, nothing is computed on the CPU ------------------------------------------------------------------------

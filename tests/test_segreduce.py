@@ -181,6 +181,127 @@ def test_layouts_reach_their_paths(name):
     assert JOIN == 256 and WAVE == 64
 
 
+# -- the layouts of tests/test_gpu_segreduce_paths.py --------------------------------------------------------------------------------------
+
+def test_old_layouts_never_put_three_starts_into_a_thread():
+    """what the layouts above leave out: at most 2 starts in a thread, off[S] never on a thread edge inside a tile nor at a tile's last
+    element (at its second element only as off[S] = n = 2^24 + 4097, in the two-tile layouts)"""
+    new = {"three or more starts in a thread", "16 starts in a thread", "4096 starts in a tile", "empty between one-element segments",
+           "stop on a thread edge inside a tile", "stop at a tile's last element"}
+    for name, (make, _) in LAYOUT_PATHS.items():
+        assert not (paths(*make()) & new), name
+
+
+def test_dense_layouts_reach_their_paths():
+    want = {"every element": {"16 starts in a thread", "three or more starts in a thread", "4096 starts in a tile"},
+            "ones and empties": {"three or more starts in a thread", "empty between one-element segments", "empty"},
+            "thread edges": {"boundary on a thread edge", "boundary one element behind a thread edge", "inside a thread"}}
+    for name, make in R.DENSE.items():
+        n, off = make()
+        o = off.astype(np.int64)
+        assert o[0] == 3 and o[-1] == 3 + 2 * TILE + 37 and n == o[-1] + 5 and np.all(o[1:] >= o[:-1])
+        got = paths(n, off)
+        assert want[name] <= got, f"{name}: missing {want[name] - got}"
+        assert {"off[0] > 0", "off[S] < n"} <= got
+    o = R.layout_ones_and_empties()[1].astype(np.int64)
+    assert np.diff(o)[:7].tolist() == [1, 0, 2, 0, 0, 1, 3] and np.bincount(o[:-1][np.diff(o) > 0] // R.KPT).max() >= 4
+    o = R.layout_thread_edges()[1].astype(np.int64)
+    assert o[:5].tolist() == [3, 16, 32, 33, 48] and "16 starts in a thread" not in paths(*R.layout_thread_edges())
+
+
+def test_position_layouts_reach_their_stops():
+    layouts = R.position_layouts()
+    P = R.POSITIONS
+    assert len(layouts) == len(P) * (len(P) - 1) // 2 + 10 + 2 and all(n == 3 * TILE for n, _ in layouts)
+    got = set()
+    for n, off in layouts:
+        o = off.astype(np.int64)
+        assert np.all(o[1:] > o[:-1]) and o[-1] <= n
+        got |= paths(n, off)
+    assert {"stop on a thread edge inside a tile", "stop at a tile's second element", "stop at a tile's last element", "ends on a tile edge",
+            "boundary at a tile's first element", "boundary at a tile's last element", "inside a thread", "join: one wave"} <= got
+    two = [off.astype(np.int64)[1] for _, off in layouts if len(off) == 3]
+    assert two == [15, 16, 17, 1023, 1024, 4095, 4096, 4097, 8191, 8192]
+    # off[S] on a thread edge inside a tile with off[0] in an earlier thread of that tile or in an earlier tile: the stop is the first flag of
+    # thread hi / 16 (j0 == 0, tid > 0) and closes a segment by ids.last or by lead[]
+    ends = [(int(off[0]), int(off[-1])) for _, off in layouts if len(off) == 2]
+    assert (17, 1024) in ends and (15, 16) in ends                  # ... by ids.last: the segment began in this tile
+    assert (5, TILE + 1024) in ends and (5, 2 * TILE + 16) in ends  # ... by lead[]: it began one and two tiles earlier
+
+
+def test_two_joins_layout_schedules_both_orders():
+    """from the offsets alone (no 18M values): the join's workgroups 5, 105 and 125 take a second open tile"""
+    n, off = R.layout_two_joins()
+    assert (n + TILE - 1) // TILE == 4401 and R.chunk_of(n) == 2 and R.join_grid(n, len(off) - 1) == 4096
+    sched = R.join_schedule(n, off)
+    # (the segment that begins in tile 4221 ends at n - 4 in tile 4400: 179 tiles behind it)
+    assert sched == {0: [(0, 5)], 5: [(5, 30), (4101, 100)], 35: [(35, 70)], 105: [(105, 195), (4201, 20)], 300: [(300, 3801)], 125: [(4221, 179)]}
+    kind = lambda m: "one wave" if m <= WAVE else "four waves"
+    orders = {tuple(kind(m) for _, m in tiles) for tiles in sched.values() if len(tiles) == 2}
+    assert orders == {("one wave", "four waves"), ("four waves", "one wave")}
+    assert max(m for tiles in sched.values() for _, m in tiles) > 2 * JOIN and -(-3801 // JOIN) == 15        # more than 2 partials a thread
+    assert sched[125][0][0] >= 4096                                 # a second trip without a first join
+    # the tile kernel: a boundary inside the first tile of a workgroup and inside the second tile of one
+    o = off.astype(np.int64)
+    inner = o[1:-1] // TILE
+    assert np.any(inner % 2 == 0) and np.any(inner % 2 == 1)
+    got = paths(n, off)
+    assert {"two tiles per workgroup", "join: one wave", "join: four waves", "join: more than one partial per thread"} <= got
+    # 4097 tiles is the least at which a workgroup of the join gets a second tile
+    assert R.join_grid(4096 * TILE, 1) == 4096 and (4097 * TILE + TILE - 1) // TILE > 16 * R.CUS
+
+
+def test_million_segments_layout_needs_a_second_trip():
+    n, off = R.layout_million_segments()
+    S = len(off) - 1
+    assert S == (1 << 20) + 4099 and S > 256 * 16 * 256 and R.join_grid(n, S) * JOIN < S
+    o = off.astype(np.int64)
+    assert o[0] == 5 and n == o[-1] + 5 and np.diff(o)[:6].tolist() == [1, 0, 2, 0, 0, 1] and 650000 < n < 750000
+    assert R.dense_paths(o) >= {"empty between one-element segments", "three or more starts in a thread"}
+    assert np.count_nonzero(np.diff(o)[1 << 20:] == 0) > 2000      # empty segments among those of the second trip
+
+
+def special_values(vt, n, rng):
+    """values whose sums are exact in the wide format in any order (whole multiples of 2^-10 below 2^10), with NaN, +-inf and +-0.0 for floats"""
+    vt = np.dtype(vt)
+    if vt.kind == "i":
+        info = np.iinfo(vt)
+        return rng.integers(info.min, info.max, n, dtype=vt, endpoint=True)
+    v = (rng.integers(-(1 << 20), 1 << 20, n) / 1024.0).astype(vt)
+    pick = rng.integers(0, 40, n)
+    for code, special in enumerate((np.nan, np.inf, -np.inf, 0.0, -0.0)):
+        v[pick == code] = special
+    return v
+
+
+@pytest.mark.parametrize("vt", [np.int32, np.int64, np.float32, np.float64], ids=lambda d: np.dtype(d).name)
+@pytest.mark.parametrize("op", R.OPS)
+def test_fast_referee_equals_loop_referee(vt, op):
+    rng = np.random.default_rng(R.OPS.index(op) * 4 + np.dtype(vt).itemsize)
+    layouts = [R.layout_ragged, R.layout_many_empty, R.layout_all_empty, lambda: (100, None)] + list(R.DENSE.values())
+    arg = op in ("argmin", "argmax")
+    for make in layouts:
+        n, off = make()
+        for ties in (False, True):
+            v = rng.integers(-2, 3, n).astype(vt) if ties else special_values(vt, n, rng)
+            if ties and np.dtype(vt).kind == "f":
+                v[rng.integers(0, 9, n) == 0] = -0.0
+            want, widx = reduce_oracle(v, off, op)
+            got, gidx = R.reduce_fast(v, off, op)
+            assert got.dtype == want.dtype and got.shape == want.shape
+            if arg:
+                assert np.array_equal(gidx, widx) and got.tobytes() == want.tobytes()          # the element itself: its bits
+            else:
+                assert gidx is None and widx is None
+                assert np.array_equal(got, want, equal_nan=np.dtype(vt).kind == "f")          # (the sign of a zero result is numpy's choice)
+            if np.dtype(vt).kind == "f":
+                (m, mag), (fm, fmag) = reduce_terms(v, off), R.terms_fast(v, off)
+                assert np.array_equal(m, fm) and np.array_equal(mag, fmag, equal_nan=True)
+                inside = v if off is None else v[int(off[0]):int(off[-1])]
+                if np.dtype(vt).kind == "f" and not ties and inside.size > 1000:
+                    assert np.isnan(inside).any() and np.isinf(inside).any() and np.any((inside == 0) & np.signbit(inside)) and np.any((inside == 0) & ~np.signbit(inside))
+
+
 def test_no_cpu_path(rsx):
     lib = rsx.load_library()
     assert lib.rsx_segmented_reduce(None, None, 16, None, 1, 0, 0, 0, None, None) == 4            # a null engine is refused
