@@ -698,6 +698,42 @@ int rsx_segmented_histogram(rsx_engine* e, const void* d_keys, uint64_t n, const
 int rsx_segmented_reduce(rsx_engine* e, const void* d_values, uint64_t n, const uint64_t* d_offsets /* or NULL */, uint64_t num_segments,
                          uint32_t flags /* must be 0 */, uint32_t op, uint32_t value_kind, void* d_values_out /* or NULL for the arg ops */,
                          uint32_t* d_index_out /* arg ops only */);
+/* rsx_segmented_expand: from offsets back to elements (moderngpu's load-balancing search / interval expand; the decode that
+ *   cub::DeviceRunLengthEncode lacks; torch.repeat_interleave with a ranged-gather form).  Nothing is sorted and there are no keys: any
+ *   engine serves, whatever its key kind or has_payload.
+ *   RESULT.  Let s(i) be the LARGEST s with off[s] <= i, the merge's rule: of several segments that share an offset the last one owns
+ *   the position, so an empty segment owns nothing.  For every i in [off[0], off[S]):
+ *     d_segment_out[i] = s(i)
+ *     d_rank_out[i]    = i - off[s(i)]
+ *     d_values_out[i]  = d_values[s(i)]                             fill form (flags == 0): num_values must equal num_segments
+ *     d_values_out[i]  = d_values[starts[s(i)] + i - off[s(i)]]     gather form (RSX_EXPAND_GATHER): segment s is a copy of
+ *                                                                   d_values[starts[s] .. starts[s] + len_s); ranges may overlap, descend
+ *                                                                   and be odd
+ *   Values are opaque bits of value_bytes = 4 or 8 bytes.  n is the element count of every output buffer given; positions outside
+ *   [off[0], off[S]) are NOT written.  At least one output must be non-NULL; d_values and d_values_out are both NULL or both given;
+ *   d_starts (num_segments entries) must be given if and only if RSX_EXPAND_GATHER is set.  num_segments == 0 or n == 0 launches nothing.
+ *   ALIGNMENT.  Every pointer is aligned to its element and no further: the kernel stores 16 bytes at a time over the part of each
+ *   4096-position tile that is 16-byte aligned in the output at hand and single elements at the ragged ends, per output.
+ *   BAD INPUT is a pair with off[s+1] < off[s] or off[s+1] > n and, in gather form, a segment with starts[s] + len_s > num_values
+ *   (empty segments included).  Then NOTHING is written and the next rsx_sync / rsx_check_status reports RSX_CALCULATION_FAILED once,
+ *   naming this call and the first such segment; the engine stays usable.
+ *   THE OUTPUT IS A FUNCTION OF THE INPUTS ALONE: no atomic touches it and no workgroup waits for another, so equal input gives equal
+ *   bits eagerly, captured, and on any stream or engine.  Launches in stream order: the checks, one bisection per tile boundary of the
+ *   ABSOLUTE grid of 4096 output positions, one pass over the tiles (a tile with no segment start in it is a pure fill; otherwise the
+ *   starts are marked in LDS and a max-scan spreads them; rsx_expand.hpp).  A tile that holds more offsets than slots (dense empty
+ *   segments) walks them 1024 at a time: slow, correct.
+ *   THE ENGINE'S SORT STATE IS UNTOUCHED: the call uses none of the capacity-sized buffers (tiles + 1 words of scratch grow, outside
+ *   stream captures), so n may exceed the capacity and an earlier sort's result stays valid.  n <= 2^31, fewer than 2^32 - 1 segments.
+ *   Asynchronous on the engine's stream, nothing read back, every launch sized from n and num_segments, capturable once a call of this
+ *   size has run.
+ *   REFUSED AT ONCE: RSX_CALCULATION_FAILED for a null engine, flag bits other than RSX_EXPAND_GATHER, value_bytes not 4 or 8, d_starts
+ *   without the flag or the flag without d_starts, one of d_values / d_values_out without the other, no output at all, the fill form
+ *   with num_values != num_segments, 2^32 - 1 segments or more, n > 2^31; RSX_HOST_BUFFERS_FAILED for null offsets, a pointer not
+ *   aligned to its element, an output overlapping an input or another output, anything overlapping the engine's buffers. */
+#define RSX_EXPAND_GATHER 64       /* flags bit 6 (bits 0-5 are taken): ranged gather instead of fill */
+int rsx_segmented_expand(rsx_engine* e, const void* d_values /* or NULL */, uint64_t num_values, uint32_t value_bytes /* 4 or 8 */,
+                         const uint64_t* d_offsets, uint64_t num_segments, uint64_t n, const uint64_t* d_starts /* gather form only, else NULL */,
+                         uint32_t flags, void* d_values_out /* or NULL */, uint32_t* d_segment_out /* or NULL */, uint32_t* d_rank_out /* or NULL */);
 /* Receive buffers other ranks can write to (the peer-store exchange below): rsx_peer_alloc (hipMalloc + an IPC handle to hand to the other
  * PROCESSES, which map it with rsx_peer_open / rsx_peer_close — peer access over xGMI); ranks that are threads of one process use the
  * pointer itself (after rsx_peer_enable, once per other device). */

@@ -43,6 +43,7 @@ VALUE_INT32, VALUE_INT64, VALUE_FLOAT32, VALUE_FLOAT64 = 0, 1, 2, 3           # 
 SCAN_EXCLUSIVE = 2         # RSX_SCAN_EXCLUSIVE: flags bit 1 of rsx_segmented_scan
 SEARCH_RIGHT = 4           # RSX_SEARCH_RIGHT: flags bit 2 of rsx_segmented_search
 COMPACT_PARTITION, COMPACT_INVERT, COMPACT_STRICT = 8, 16, 32                  # RSX_COMPACT_*: flags bits 3, 4, 5 of rsx_segmented_compact
+EXPAND_GATHER = 64         # RSX_EXPAND_GATHER: flags bit 6 of rsx_segmented_expand
 SET_INTERSECTION, SET_DIFFERENCE, SET_UNION, SET_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3       # RSX_SET_*: op of rsx_segmented_set_op
 # rsx_experimental_option (include/radixsort_hip_experiments.h): known to the EXPERIMENTS build only (experiments()); the product library refuses them
 XOPT_DEBUG_RAISE_SCAN_TIMEOUT, XOPT_INLINE_SCAN, XOPT_INLINE_SCAN_MAX_GROUPS, XOPT_REORDER8_KERNEL, XOPT_REORDER8_STAY = 16, 17, 18, 19, 20
@@ -54,7 +55,7 @@ SYMBOLS = [
     "rsx_create", "rsx_destroy", "rsx_set_stream", "rsx_get_stream", "rsx_set_option", "rsx_get_geometry", "rsx_resize",
     "rsx_upload", "rsx_fill_pad", "rsx_download", "rsx_pin_host", "rsx_unpin_host", "rsx_pipeline_submit", "rsx_pipeline_wait", "rsx_host_device_pointer",
     "rsx_histogram", "rsx_scan", "rsx_paste", "rsx_reorder", "rsx_sort", "rsx_sync", "rsx_check_status",
-    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_segmented_merge", "rsx_segmented_set_op", "rsx_segmented_histogram", "rsx_segmented_reduce", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
+    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_segmented_merge", "rsx_segmented_set_op", "rsx_segmented_histogram", "rsx_segmented_reduce", "rsx_segmented_expand", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
 ]
 
 
@@ -171,6 +172,7 @@ def load_library() -> C.CDLL:
         "rsx_segmented_set_op": ([P, P, P, U64, P, P, P, U64, P, U64, C.c_uint32, C.c_uint32, P, P, P, P, P], I),
         "rsx_segmented_histogram": ([P, P, U64, P, U64, P, U64, U64, C.c_uint32, U64, C.c_uint32, P], I),
         "rsx_segmented_reduce": ([P, P, U64, P, U64, C.c_uint32, C.c_uint32, C.c_uint32, P, P], I),
+        "rsx_segmented_expand": ([P, P, U64, C.c_uint32, P, U64, U64, P, C.c_uint32, P, P, P], I),
         "rsx_msd_count": ([P, P, U64, I, I, P], I),
         "rsx_msd_scatter": ([P, P, P, U64, P, P], I),
         "rsx_msd_plan": ([P, P, C.c_uint32, C.c_uint32, I, I, P], I),
@@ -527,6 +529,21 @@ class Engine:
         self._check(self.lib.rsx_segmented_reduce(
             self._h, C.c_void_p(d_values) if d_values else None, n, C.c_void_p(d_offsets) if d_offsets else None, num_segments, 0, op, value_kind,
             C.c_void_p(d_values_out) if d_values_out else None, C.c_void_p(d_index_out) if d_index_out else None), "rsx_segmented_reduce")
+
+    def segmented_expand(self, d_values: int | None, num_values: int, value_bytes: int, d_offsets: int | None, num_segments: int, n: int,
+                         d_starts: int | None = None, d_values_out: int | None = None, d_segment_out: int | None = None,
+                         d_rank_out: int | None = None) -> None:
+        """From offsets back to elements: for every position i of [off[0], off[S]) the segment s(i) that owns it (the largest s with
+        off[s] <= i: empty segments own nothing) into d_segment_out[i], i - off[s(i)] into d_rank_out[i] (both uint32) and a value of
+        value_bytes = 4 or 8 opaque bytes into d_values_out[i]: d_values[s(i)] (fill form, num_values == num_segments) or, with
+        d_starts, d_values[starts[s(i)] + rank] (gather form, EXPAND_GATHER).  n is the element count of the outputs; positions outside
+        [off[0], off[S]) are not written.  Any subset of the outputs, at least one; pointers need their element's alignment only.  n may
+        exceed the capacity and the engine's sort result is left alone.  Asynchronous on the engine's stream; bad offsets or starts
+        (nothing is written then) are reported by the next sync() / check_status()."""
+        self._check(self.lib.rsx_segmented_expand(
+            self._h, C.c_void_p(d_values) if d_values else None, num_values, value_bytes, C.c_void_p(d_offsets) if d_offsets else None, num_segments, n,
+            C.c_void_p(d_starts) if d_starts else None, EXPAND_GATHER if d_starts else 0, C.c_void_p(d_values_out) if d_values_out else None,
+            C.c_void_p(d_segment_out) if d_segment_out else None, C.c_void_p(d_rank_out) if d_rank_out else None), "rsx_segmented_expand")
 
     def segmented_search(self, d_sorted: int | None, n: int, d_offsets: int | None, num_segments: int, d_queries: int, num_queries: int,
                          d_query_offsets: int | None, d_index_out: int, right: bool = False) -> None:
@@ -1474,6 +1491,207 @@ def argmax(x, dim: int = -1, keepdim: bool = False):
 def argmin(x, dim: int = -1, keepdim: bool = False):
     """torch.argmin(x, dim) on a device tensor: the first minimum of every row, a NaN beating every number."""
     return _reduce_along("argmin", x, "argmin", dim, keepdim, False, False)[1]
+
+
+# -- expand on torch tensors ------------------------------------------------------------------------------------------------------------
+_EXPAND_VIEWS = {4: "int32", 8: "int64"}
+
+
+def _expand_offsets(what: str, offsets, torch):
+    if offsets is None or not hasattr(offsets, "is_cuda") or not offsets.is_cuda:
+        raise ValueError(f"{what}: offsets must be a device tensor (there is no CPU path)")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1:
+        raise ValueError(f"{what}: offsets must be a 1-D int64 device tensor")
+    return offsets if offsets.is_contiguous() else offsets.contiguous()
+
+
+def _expand_total(what: str, off, n):
+    """The element count of the outputs: n as given (no synchronisation), else offsets[-1] read back once, as torch does."""
+    if n is None:
+        n = int(off[-1].item()) if off.numel() else 0
+    n = int(n)
+    if n < 0 or n > (1 << 31):
+        raise ValueError(f"{what}: n must lie in [0, 2^31] (rsx_segmented_expand's bound)")
+    return n
+
+
+def _expand_call(what: str, off, n: int, values=None, starts=None, want_segment: bool = False, want_rank: bool = False, fill=None):
+    """One rsx_segmented_expand call.  values: 1-D contiguous device tensor of 4- or 8-byte elements or None; returns (values_out or None,
+    int32 segment ids or None, int32 ranks or None), each of n elements; positions outside [off[0], off[-1]) hold `fill` (default 0)."""
+    import torch
+    dev = off.device
+    nseg = max(off.numel() - 1, 0)
+    vout = sout = rout = None
+    if values is not None:
+        vout = torch.zeros(n, dtype=values.dtype, device=dev) if fill is None else torch.full((n,), fill, dtype=values.dtype, device=dev)
+    if want_segment:
+        sout = torch.zeros(n, dtype=torch.int32, device=dev)
+    if want_rank:
+        rout = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n and nseg:
+        device = dev.index if dev.index is not None else torch.cuda.current_device()
+        eng = _scan_engine(device, torch.cuda.current_stream(dev).cuda_stream, 4)
+        eng.segmented_expand(None if values is None else values.data_ptr(), 0 if values is None else values.numel(),
+                             4 if values is None else values.element_size(), off.data_ptr(), nseg, n,
+                             None if starts is None else starts.data_ptr(), None if vout is None else vout.data_ptr(),
+                             None if sout is None else sout.data_ptr(), None if rout is None else rout.data_ptr())
+        eng.check_status()      # reports bad input of calls that have already finished; no synchronisation
+    return vout, sout, rout
+
+
+def _expand_values(what: str, off, n: int, values, starts, want_segment: bool, want_rank: bool):
+    """values of any dtype and shape [num_values, ...]: 4- and 8-byte 1-D values go through the kernel, everything else expands indices
+    (the kernel again) and uses torch.index_select."""
+    import torch
+    if not values.is_cuda or values.device != off.device:
+        raise ValueError(f"{what}: values must be a device tensor on the offsets' device (there is no CPU path)")
+    nseg = max(off.numel() - 1, 0)
+    if starts is None and values.shape[0] != nseg:
+        raise ValueError(f"{what}: the fill form has one value per segment ({nseg}), not {values.shape[0]}")
+    if values.dim() == 1 and values.element_size() in _EXPAND_VIEWS and not values.is_complex():
+        v = values if values.is_contiguous() else values.contiguous()
+        if v.numel() == 0:
+            v = torch.zeros(1, dtype=values.dtype, device=values.device)      # (nothing can be read from it: n or S is 0, or the starts are refused)
+        vout, sout, rout = _expand_call(what, off, n, v, starts, want_segment, want_rank)
+        return vout, sout, rout
+    if starts is None:
+        _, sout, rout = _expand_call(what, off, n, None, None, True, want_rank)
+        return torch.index_select(values, 0, sout.to(torch.int64)), sout if want_segment else None, rout
+    iota = torch.arange(values.shape[0], device=values.device, dtype=torch.int64)
+    idx, sout, rout = _expand_call(what, off, n, iota, starts, want_segment, want_rank)
+    return torch.index_select(values, 0, idx), sout, rout
+
+
+def segmented_expand(offsets, values=None, n=None, starts=None, return_segment: bool = False, return_rank: bool = False):
+    """From offsets back to elements in ONE engine call (rsx_segmented_expand).  For every position i of [offsets[0], offsets[-1]): the
+    segment s(i) that owns it (the largest s with offsets[s] <= i, so empty segments own nothing), its rank i - offsets[s(i)], and, with
+    `values`, values[s(i)] (one value per segment) or, with `starts` (int64, one per segment), values[starts[s(i)] + rank]: segment s is a
+    copy of values[starts[s] : starts[s] + length].  Returns values[, segment][, rank] (just the ids and / or ranks without values; int64),
+    each of n elements.  n is the length of the result: given, nothing synchronises with the host; None reads offsets[-1] back once.
+    Positions outside [offsets[0], offsets[-1]) hold 0.  Bad offsets or starts (nothing is written then) raise RadixSortError at a later
+    call or synchronisation of the engine."""
+    import torch
+    off = _expand_offsets("segmented_expand", offsets, torch)
+    n = _expand_total("segmented_expand", off, n)
+    st = None
+    if starts is not None:
+        if values is None:
+            raise ValueError("segmented_expand: starts go with values")
+        if not hasattr(starts, "is_cuda") or not starts.is_cuda or starts.dtype != torch.int64 or starts.dim() != 1 or starts.numel() != max(off.numel() - 1, 0) or starts.device != off.device:
+            raise ValueError("segmented_expand: starts must be a 1-D int64 device tensor with one entry per segment")
+        st = starts if starts.is_contiguous() else starts.contiguous()
+    if values is None:
+        if not (return_segment or return_rank):
+            raise ValueError("segmented_expand: nothing to return (values, return_segment or return_rank)")
+        _, sout, rout = _expand_call("segmented_expand", off, n, None, None, return_segment, return_rank)
+        res = [t.to(torch.int64) for t in (sout, rout) if t is not None]
+        return res[0] if len(res) == 1 else tuple(res)
+    vout, sout, rout = _expand_values("segmented_expand", off, n, values, st, return_segment, return_rank)
+    res = [vout] + [t.to(torch.int64) for t, w in ((sout, return_segment), (rout, return_rank)) if w]
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def segment_ids(offsets, n=None):
+    """The segment id of every element (CSR -> COO): int64, n entries (None: offsets[-1], read back once)."""
+    return segmented_expand(offsets, n=n, return_segment=True)
+
+
+def segment_ranks(offsets, n=None):
+    """The position of every element inside its segment: int64, n entries (None: offsets[-1], read back once)."""
+    return segmented_expand(offsets, n=n, return_rank=True)
+
+
+def broadcast_segments(per_segment, offsets, n=None):
+    """The [S] result of segmented_reduce (or any tensor with one entry, or one row, per segment) spread over the segments' elements:
+    out[i] = per_segment[s(i)], n entries (None: offsets[-1], read back once)."""
+    import torch
+    off = _expand_offsets("broadcast_segments", offsets, torch)
+    n = _expand_total("broadcast_segments", off, n)
+    return _expand_values("broadcast_segments", off, n, per_segment, None, False, False)[0]
+
+
+def _offsets_of(what: str, lengths, torch):
+    """[0, cumsum(lengths)] with the library's own scan, on int64; negative lengths make descending pairs, which the call reports."""
+    if not hasattr(lengths, "is_cuda") or not lengths.is_cuda:
+        raise ValueError(f"{what}: lengths must be a device tensor (there is no CPU path)")
+    if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+        raise ValueError(f"{what}: lengths must be a 1-D integer tensor")
+    off = torch.zeros(lengths.numel() + 1, dtype=torch.int64, device=lengths.device)
+    if lengths.numel():
+        off[1:] = lengths.to(torch.int64)
+        off = _scan_call(what, None, off, None, "sum", False, off)
+    return off
+
+
+def repeat_interleave(x, repeats=None, dim=None, output_size=None):
+    """torch.repeat_interleave in its three call forms: (repeats_tensor) -> the index i repeated repeats[i] times; (x, int) and
+    (x, repeats_tensor), over the flattened x or along `dim`.  With output_size nothing synchronises with the host; without it the
+    total is read back once, as torch does.  1-D values of 4 and 8 bytes go through rsx_segmented_expand itself; other dtypes, and `dim`
+    on N-D input, expand indices and use torch.index_select.  An int `repeats` uses uniform offsets.  Negative repeats are reported as bad
+    offsets at a later call or synchronisation of the engine."""
+    import torch
+    if not hasattr(x, "is_cuda") or not x.is_cuda:
+        raise ValueError("repeat_interleave: x must be a device tensor (there is no CPU path)")
+    if repeats is None:                                                          # form 1: x holds the repeats
+        off = _offsets_of("repeat_interleave", x, torch)
+        n = _expand_total("repeat_interleave", off, output_size)
+        return _expand_call("repeat_interleave", off, n, None, None, True, False)[1].to(torch.int64)
+    if dim is None:
+        x = x.reshape(-1)
+        dim = 0
+    dim = dim % max(x.dim(), 1)
+    if x.dim() == 0:
+        x = x.reshape(1)
+    size = x.shape[dim]
+    if isinstance(repeats, int) or (hasattr(repeats, "dim") and repeats.dim() == 0 and not repeats.is_cuda):
+        r = int(repeats)
+        if r < 0:
+            raise ValueError("repeat_interleave: repeats must not be negative")
+        off = torch.arange(0, size + 1, device=x.device, dtype=torch.int64) * r
+        n = size * r
+        if output_size is not None and int(output_size) != n:
+            raise ValueError("repeat_interleave: output_size does not match size * repeats")
+    else:
+        if not repeats.is_cuda:
+            raise ValueError("repeat_interleave: repeats must be an int or a device tensor (there is no CPU path)")
+        rep = repeats.reshape(-1)
+        if rep.numel() == 1 and size != 1:
+            rep = rep.expand(size)
+        if rep.numel() != size:
+            raise ValueError("repeat_interleave: repeats must have one entry per element along dim")
+        off = _offsets_of("repeat_interleave", rep, torch)
+        n = _expand_total("repeat_interleave", off, output_size)
+    if x.dim() == 1:
+        return _expand_values("repeat_interleave", off, n, x, None, False, False)[0]
+    sout = _expand_call("repeat_interleave", off, n, None, None, True, False)[1]
+    return torch.index_select(x, dim, sout.to(torch.int64))
+
+
+def gather_ranges(src, starts, lengths):
+    """The ragged slices src[starts[s] : starts[s] + lengths[s]] packed one behind the other: returns (values, offsets) with offsets =
+    [0, cumsum(lengths)] (int64).  Slices may overlap and come in any order.  The total is read back once (the result's size)."""
+    import torch
+    off = _offsets_of("gather_ranges", lengths, torch)
+    if not hasattr(starts, "is_cuda") or not starts.is_cuda or starts.dim() != 1 or starts.numel() != lengths.numel():
+        raise ValueError("gather_ranges: starts must be a 1-D device tensor with one entry per slice")
+    st = starts.to(torch.int64).contiguous()
+    n = _expand_total("gather_ranges", off, None)
+    flat = src if src.dim() >= 1 else src.reshape(1)
+    return _expand_values("gather_ranges", off, n, flat, st, False, False)[0], off
+
+
+def pack_rows(x, lengths):
+    """A padded batch x of shape [B, W(, ...)] to ragged storage: row b contributes its first lengths[b] entries.  Returns (values,
+    offsets); the slice of row b starts at b * W.  The total is read back once (the result's size)."""
+    import torch
+    if not hasattr(x, "is_cuda") or not x.is_cuda or x.dim() < 2:
+        raise ValueError("pack_rows: x must be a device tensor of shape [B, W, ...]")
+    B, W = x.shape[0], x.shape[1]
+    if not hasattr(lengths, "numel") or lengths.numel() != B:
+        raise ValueError("pack_rows: lengths must have one entry per row")
+    starts = torch.arange(0, B, device=x.device, dtype=torch.int64) * W
+    flat = (x if x.is_contiguous() else x.contiguous()).reshape((B * W,) + tuple(x.shape[2:]))
+    return gather_ranges(flat, starts, lengths.reshape(-1))
 
 
 def max_rows(x, dim: int = -1, keepdim: bool = False):

@@ -237,6 +237,9 @@ struct rsx_engine {
     // rsx_segmented_merge (capi_merge.inc): the segment and merge-path split of every tile boundary
     rsx::MergeSplit* merge_split = nullptr;
     uint64_t merge_split_cap = 0;
+    // rsx_segmented_expand (capi_expand.inc): the number of offsets below every tile boundary of the absolute output grid
+    uint32_t* expand_split = nullptr;
+    uint64_t expand_split_cap = 0;
 
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -1257,6 +1260,7 @@ constexpr uint32_t kStatusCallMerge = 1;         // word 1 of the mapped status 
 constexpr uint32_t kStatusCallSetop = 2;
 constexpr uint32_t kStatusCallHistogram = 3;
 constexpr uint32_t kStatusCallReduce = 4;
+constexpr uint32_t kStatusCallExpand = 5;
 int check_scan_timeout(rsx_engine* e, int status)
 {
     if (e->seg_status_host) {
@@ -1281,6 +1285,10 @@ int check_scan_timeout(rsx_engine* e, int status)
             if (call == kStatusCallReduce)
                 return fail(status, ("rsx_segmented_reduce: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; nothing was written (the "
                                      "first such segment of the call; reported once; the engine remains usable)").c_str());
+            if (call == kStatusCallExpand)
+                return fail(status, ("rsx_segmented_expand: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n, or in gather form "
+                                     "starts[s] + its length > num_values; nothing was written (the first such segment of the call; reported once; the "
+                                     "engine remains usable)").c_str());
             return fail(status, ("rsx_segmented_sort / rsx_segmented_topk / rsx_segmented_select: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; it was neither read nor "
                                  "written (the first such segment of the call; reported once; the engine remains usable)").c_str());
         }
@@ -1649,7 +1657,8 @@ int rsx_destroy(rsx_engine* e)
     for (void* p : {static_cast<void*>(e->seg_hdr), static_cast<void*>(e->seg_temp), static_cast<void*>(e->seg_bsum), static_cast<void*>(e->seg_list),
                     static_cast<void*>(e->seg_large), static_cast<void*>(e->seg_tstart), static_cast<void*>(e->seg_table), static_cast<void*>(e->seg_gsum),
                     static_cast<void*>(e->seg_gsum2), static_cast<void*>(e->topk_state), static_cast<void*>(e->topk_start),
-                    static_cast<void*>(e->topk_cont), static_cast<void*>(e->uniq_iota), static_cast<void*>(e->red_part), static_cast<void*>(e->merge_split)}) {
+                    static_cast<void*>(e->topk_cont), static_cast<void*>(e->uniq_iota), static_cast<void*>(e->red_part), static_cast<void*>(e->merge_split),
+                    static_cast<void*>(e->expand_split)}) {
         if (p && hipFree(p) != hipSuccess) status = RSX_CLEANUP_FAILED;
     }
     if (e->seg_status_host && hipHostFree(e->seg_status_host) != hipSuccess) status = RSX_CLEANUP_FAILED;
@@ -2410,6 +2419,7 @@ int rsx_peer_enable(rsx_engine* e, int peer_device)
 #include "capi_setop.inc"
 #include "capi_histogram.inc"
 #include "capi_segreduce.inc"
+#include "capi_expand.inc"
 
 int rsx_key_range(rsx_engine* e, const void* d_keys, uint64_t n, uint64_t* lo, uint64_t* hi)
 {

@@ -37,6 +37,7 @@
 //   rsx_radix8.hpp     histogram8 / scan8_* / reorder8
 //   rsx_util.hpp       reference-geometry diagnostics and the small helpers of the multi-GPU partition
 //   rsx_msd.hpp        the sharded sort's exchange step on the top B <= 8 bits: wave-major bucket starts, device-side plan, per-wave push
+//   rsx_expand.hpp     expand_starts / expand_split / expand_tile (rsx_segmented_expand: offsets back to elements; no sort kernel in it)
 #pragma once
 
 #include "rsx_common.hpp"
@@ -47,6 +48,7 @@
 #include "rsx_radix8.hpp"
 #include "rsx_util.hpp"
 #include "rsx_msd.hpp"
+#include "rsx_expand.hpp"
 #ifdef RSX_EXPERIMENTS
 #include "rsx_radix8_experiments.hpp"      // rejected alternatives, A/B builds only
 #endif
