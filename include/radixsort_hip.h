@@ -591,7 +591,8 @@ int rsx_segmented_merge(rsx_engine* e, const void* d_a, const uint32_t* d_a_payl
  *   total (S + 1 uint64; REQUIRED).  d_keys_out gets the keys (bits unchanged); d_payload_out the 32-bit word that came with each key (the
  *   two payload inputs and d_payload_out are all given or all NULL); d_index_out the position in A_s ++ B_s, the merge's convention
  *   (below La: A_s[j], otherwise B_s[j - La]); d_match_out (RSX_SET_INTERSECTION only) for the kept A occurrence r of x the position
- *   relative to boff[s] of B's occurrence r of x: index and match together are an inner join.  Each of these four may be NULL; with all
+ *   relative to boff[s] of B's occurrence r of x: index and match together are an inner join where no key repeats
+ *   (min(m, n) pairs of a key's m x n otherwise: rsx_segmented_join is the relational join).  Each of these four may be NULL; with all
  *   NULL the call only counts.  Nothing at or past koff[S] is written in any output.  BUFFER SIZES: na elements for intersection and
  *   difference, na + nb for union and symmetric difference; the overlap checks use these sizes.
  *   INPUTS THAT ARE NOT SORTED give an unspecified result; every access stays inside the buffers, koff is non-decreasing, koff[S] is at
@@ -734,6 +735,53 @@ int rsx_segmented_reduce(rsx_engine* e, const void* d_values, uint64_t n, const 
 int rsx_segmented_expand(rsx_engine* e, const void* d_values /* or NULL */, uint64_t num_values, uint32_t value_bytes /* 4 or 8 */,
                          const uint64_t* d_offsets, uint64_t num_segments, uint64_t n, const uint64_t* d_starts /* gather form only, else NULL */,
                          uint32_t flags, void* d_values_out /* or NULL */, uint32_t* d_segment_out /* or NULL */, uint32_t* d_rank_out /* or NULL */);
+/* rsx_segmented_join: the relational equi-join of sorted segment s of A, d_a[aoff[s] .. aoff[s+1]), with sorted segment s of B,
+ *   d_b[boff[s] .. boff[s+1]), for every s (moderngpu's relational join on the load-balancing search; the foreign-key lookup, edge x edge,
+ *   sparse x sparse).  Both sorted in the engine's order (key kind, direction, IEEE 754 totalOrder for floats).  Both offsets arrays NULL:
+ *   ONE segment; one without the other is refused.  Keys are equal iff their bits are: -0.0 and +0.0 do not join, NaNs of equal bits do.
+ *   Unlike RSX_SET_INTERSECTION, whose index and match outputs pair only min(m, n) of a key's m x n occurrences, every A row meets every
+ *   partner.
+ *   ROWS.  For A element i of segment s (i relative to aoff[s]) let lb_i and ub_i be the lower and the upper bound of its key in B_s and
+ *   c_i = ub_i - lb_i.  RSX_JOIN_INNER emits the c_i rows (i, lb_i + r), r < c_i.  RSX_JOIN_LEFT the same and, where c_i == 0, the one row
+ *   (i, 0xFFFFFFFF).  RSX_JOIN_SEMI the one row (i, lb_i) iff c_i > 0.  RSX_JOIN_ANTI the one row (i, -) iff c_i == 0 (d_b_index_out is
+ *   refused).  Rows are ordered by segment, then i, then B position, and packed from 0: row p writes d_a_index_out[p] = i,
+ *   d_b_index_out[p] = the B position relative to boff[s], d_keys_out[p] = the A key, bits unchanged.  d_out_offsets[s] (uint64, S + 1
+ *   entries, required) = rows before segment s; d_out_offsets[S] = P, the total.
+ *   64-BIT COUNTS AND TRUNCATION.  P can reach La x Lb per segment; all counting is 64-bit and d_out_offsets holds the true counts
+ *   whatever out_capacity is.  out_capacity is the element count of each of the three row buffers: exactly the rows p < min(P,
+ *   out_capacity) are written and nothing at or past that position is touched.  With the three row outputs NULL the call only counts
+ *   (out_capacity is ignored): read d_out_offsets[S], allocate, call again; or size the buffers from a bound you know (P == na for a
+ *   foreign-key join, P <= na for SEMI and ANTI).  Truncation is no error: it shows as d_out_offsets[S] > out_capacity.
+ *   BAD INPUT is a pair with off[s+1] < off[s] or off[s+1] > n in either offsets array (n = na, nb).  Then d_out_offsets holds zeros,
+ *   NOTHING else is written, and the next rsx_sync / rsx_check_status reports RSX_CALCULATION_FAILED once, naming this call and the first
+ *   such segment; the engine stays usable.  Segments that are NOT SORTED give unspecified rows, but no access leaves the buffers, the
+ *   offsets are non-decreasing, exactly [0, min(P, out_capacity)) is written, every A index is < La and every B index < Lb or 0xFFFFFFFF
+ *   (ub is searched inside [lb, Lb]).  na == 0: zero offsets, no rows.  nb == 0: INNER and SEMI have no rows, LEFT and ANTI every A row.
+ *   num_segments == 0 (with offsets) launches nothing and writes nothing.
+ *   THE OUTPUT IS A FUNCTION OF THE INPUTS ALONE: no atomic decides a destination or touches an output and no workgroup waits for another,
+ *   so equal input gives equal bits eagerly, captured, and on any stream or engine.  Launches in stream order: the checks, one pass over
+ *   tiles of 4096 A positions (per element the two bounds in B_s, the row count, a 64-bit prefix inside the tile), a 64-bit scan of the
+ *   tile totals, the offsets; then, unless the call only counts, one bisection per boundary of the grid of 4096 output rows and one pass
+ *   over those tiles (rsx_join.hpp).  An output tile that spans a long run of A elements without a row (sparse matches) walks it: slow,
+ *   correct.
+ *   THE ENGINE'S SORT STATE IS UNTOUCHED: any engine whatever its has_payload; none of the capacity-sized buffers (scratch of 12 to 16
+ *   bytes per A position grows, outside stream captures), so na, nb and P may exceed the capacity and an earlier sort's result stays
+ *   valid.  Asynchronous on the engine's stream, nothing read back, every launch sized from na, nb, num_segments and out_capacity,
+ *   capturable once a call of this size has run.
+ *   REFUSED AT ONCE: RSX_CALCULATION_FAILED for a null engine, op > 3, flags != 0, one offsets array without the other, na or nb above
+ *   2^31, 2^32 - 1 segments or more, out_capacity above 2^34 with a row output (the output tile grid is 32-bit), d_b_index_out with
+ *   RSX_JOIN_ANTI; RSX_HOST_BUFFERS_FAILED for a missing d_out_offsets, null or misaligned pointers (d_a and d_b 16-byte aligned,
+ *   everything else aligned to its element), an output overlapping an input or another output, anything overlapping the engine's
+ *   buffers. */
+#define RSX_JOIN_INNER 0
+#define RSX_JOIN_LEFT  1
+#define RSX_JOIN_SEMI  2
+#define RSX_JOIN_ANTI  3
+int rsx_segmented_join(rsx_engine* e, const void* d_a, uint64_t na, const uint64_t* d_a_offsets /* or NULL */,
+                       const void* d_b, uint64_t nb, const uint64_t* d_b_offsets /* or NULL */, uint64_t num_segments,
+                       uint32_t op, uint32_t flags /* must be 0 */, uint64_t out_capacity,
+                       void* d_keys_out /* or NULL */, uint32_t* d_a_index_out /* or NULL */, uint32_t* d_b_index_out /* or NULL */,
+                       uint64_t* d_out_offsets /* required, S + 1 */);
 /* Receive buffers other ranks can write to (the peer-store exchange below): rsx_peer_alloc (hipMalloc + an IPC handle to hand to the other
  * PROCESSES, which map it with rsx_peer_open / rsx_peer_close — peer access over xGMI); ranks that are threads of one process use the
  * pointer itself (after rsx_peer_enable, once per other device). */

@@ -45,6 +45,7 @@ SEARCH_RIGHT = 4           # RSX_SEARCH_RIGHT: flags bit 2 of rsx_segmented_sear
 COMPACT_PARTITION, COMPACT_INVERT, COMPACT_STRICT = 8, 16, 32                  # RSX_COMPACT_*: flags bits 3, 4, 5 of rsx_segmented_compact
 EXPAND_GATHER = 64         # RSX_EXPAND_GATHER: flags bit 6 of rsx_segmented_expand
 SET_INTERSECTION, SET_DIFFERENCE, SET_UNION, SET_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3       # RSX_SET_*: op of rsx_segmented_set_op
+JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = 0, 1, 2, 3                                 # RSX_JOIN_*: op of rsx_segmented_join
 # rsx_experimental_option (include/radixsort_hip_experiments.h): known to the EXPERIMENTS build only (experiments()); the product library refuses them
 XOPT_DEBUG_RAISE_SCAN_TIMEOUT, XOPT_INLINE_SCAN, XOPT_INLINE_SCAN_MAX_GROUPS, XOPT_REORDER8_KERNEL, XOPT_REORDER8_STAY = 16, 17, 18, 19, 20
 EXPERIMENTS_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tools", "_variants", "libradixsort_hip_experiments.so")
@@ -55,7 +56,7 @@ SYMBOLS = [
     "rsx_create", "rsx_destroy", "rsx_set_stream", "rsx_get_stream", "rsx_set_option", "rsx_get_geometry", "rsx_resize",
     "rsx_upload", "rsx_fill_pad", "rsx_download", "rsx_pin_host", "rsx_unpin_host", "rsx_pipeline_submit", "rsx_pipeline_wait", "rsx_host_device_pointer",
     "rsx_histogram", "rsx_scan", "rsx_paste", "rsx_reorder", "rsx_sort", "rsx_sync", "rsx_check_status",
-    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_segmented_merge", "rsx_segmented_set_op", "rsx_segmented_histogram", "rsx_segmented_reduce", "rsx_segmented_expand", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
+    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_segmented_merge", "rsx_segmented_set_op", "rsx_segmented_histogram", "rsx_segmented_reduce", "rsx_segmented_expand", "rsx_segmented_join", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
 ]
 
 
@@ -173,6 +174,7 @@ def load_library() -> C.CDLL:
         "rsx_segmented_histogram": ([P, P, U64, P, U64, P, U64, U64, C.c_uint32, U64, C.c_uint32, P], I),
         "rsx_segmented_reduce": ([P, P, U64, P, U64, C.c_uint32, C.c_uint32, C.c_uint32, P, P], I),
         "rsx_segmented_expand": ([P, P, U64, C.c_uint32, P, U64, U64, P, C.c_uint32, P, P, P], I),
+        "rsx_segmented_join": ([P, P, U64, P, P, U64, P, U64, C.c_uint32, C.c_uint32, U64, P, P, P, P], I),
         "rsx_msd_count": ([P, P, U64, I, I, P], I),
         "rsx_msd_scatter": ([P, P, P, U64, P, P], I),
         "rsx_msd_plan": ([P, P, C.c_uint32, C.c_uint32, I, I, P], I),
@@ -608,6 +610,24 @@ class Engine:
         self._check(self.lib.rsx_segmented_set_op(
             self._h, opt(d_a), opt(d_a_payload), na, opt(d_a_offsets), opt(d_b), opt(d_b_payload), nb, opt(d_b_offsets), num_segments, op, flags,
             opt(d_keys_out), opt(d_payload_out), opt(d_index_out), opt(d_match_out), opt(d_out_offsets)), "rsx_segmented_set_op")
+
+    def segmented_join(self, d_a: int | None, na: int, d_a_offsets: int | None, d_b: int | None, nb: int, d_b_offsets: int | None, num_segments: int,
+                       op: int, out_capacity: int, d_out_offsets: int | None, d_a_index_out: int | None = None, d_b_index_out: int | None = None,
+                       d_keys_out: int | None = None, flags: int = 0) -> None:
+        """The equi-join (op: JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI) of sorted segment s of A, d_a[aoff[s] .. aoff[s+1]), with sorted
+        segment s of B, for every s.  An A element i (relative to aoff[s]) whose key has the lower bound lb and c partners in B_s emits:
+        INNER the rows (i, lb + r), r < c; LEFT the same and (i, 0xFFFFFFFF) where c == 0; SEMI (i, lb) iff c > 0; ANTI (i, -) iff c == 0
+        (no d_b_index_out).  Rows come by segment, A position, B position, densely packed: d_a_index_out / d_b_index_out (uint32, relative
+        to the segment), d_keys_out (the A key).  d_out_offsets (num_segments + 1 uint64, required) gets the TRUE number of rows before
+        every segment whatever out_capacity is; exactly the rows below min(total, out_capacity) are written (out_capacity: elements of each
+        row buffer).  All three row outputs None: count only.  Both offsets None: ONE segment.  Keys are equal iff their bits are.  na,
+        nb and the total may exceed the capacity, the engine's sort result is left alone, and has_payload does not matter.  Asynchronous
+        on the engine's stream; bad offsets (d_out_offsets holds zeros then, nothing else is written) are reported by the next sync() /
+        check_status()."""
+        opt = lambda p: C.c_void_p(p) if p else None
+        self._check(self.lib.rsx_segmented_join(
+            self._h, opt(d_a), na, opt(d_a_offsets), opt(d_b), nb, opt(d_b_offsets), num_segments, op, flags, out_capacity,
+            opt(d_keys_out), opt(d_a_index_out), opt(d_b_index_out), opt(d_out_offsets)), "rsx_segmented_join")
 
     def key_bits(self, value) -> int:
         """The bit pattern of the Python number `value` as a key of this engine (two's complement for integers, IEEE 754 for floats)."""
@@ -2437,3 +2457,140 @@ def union_sorted(a, b, payload_a=None, payload_b=None, descending: bool = False,
 def symmetric_difference_sorted(a, b, payload_a=None, payload_b=None, descending: bool = False, return_index: bool = False):
     """The multiset symmetric difference of two sorted device tensors along their last dimension; shapes, results and index as union_sorted."""
     return _set_rows("symmetric_difference_sorted", SET_SYMMETRIC_DIFFERENCE, a, b, payload_a, payload_b, descending, return_index, False)
+
+
+# -- joins on torch tensors -------------------------------------------------------------------------------------------------------------
+_JOIN_OPS = {"inner": JOIN_INNER, "left": JOIN_LEFT, "semi": JOIN_SEMI, "anti": JOIN_ANTI}
+
+
+def _join_code(what: str, how) -> int:
+    if isinstance(how, str) and how in _JOIN_OPS:
+        return _JOIN_OPS[how]
+    if isinstance(how, int) and not isinstance(how, bool) and 0 <= how <= 3:
+        return how
+    raise ValueError(f"{what}: unknown kind {how!r} (one of {', '.join(_JOIN_OPS)}, or JOIN_INNER .. JOIN_ANTI)")
+
+
+def _join_call(what: str, a, a_offsets, b, b_offsets, how, descending: bool, want_keys: bool, capacity):
+    """One or two rsx_segmented_join calls on 1-D device tensors (both offsets None: one segment).  Returns (ia, ib, out_offsets, keys) with
+    int64 indices, -1 for "none"; ib is None for the anti join, keys None unless asked for.  capacity None: a count-only call, ONE read-back
+    of the total, then the writing call into buffers of exactly that size.  capacity an int: one call, no synchronisation, buffers of that
+    length holding -1 (keys: 0) behind min(total, capacity)."""
+    import torch
+    for name, t in (("a", a), ("b", b)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{what}: {name} must be a tensor")
+    name = str(a.dtype).replace("torch.", "")
+    if name not in _KEY_DTYPES:
+        raise TypeError(f"{what}: unsupported key type {a.dtype}")
+    if b.dtype != a.dtype:
+        raise TypeError(f"{what}: a is {a.dtype}, b {b.dtype} (convert one of them: a join compares keys of one type)")
+    code = _join_code(what, how)
+    if not a.is_cuda or not b.is_cuda:
+        raise ValueError(f"{what}: a and b must be device tensors (there is no CPU path)")
+    if a.dim() != 1 or b.dim() != 1 or b.device != a.device:
+        raise ValueError(f"{what}: a and b must be 1-D tensors on one device")
+    if (a_offsets is None) != (b_offsets is None):
+        raise ValueError(f"{what}: a_offsets and b_offsets must both be given or both be None")
+    for oname, o in (("a_offsets", a_offsets), ("b_offsets", b_offsets)):
+        if o is not None and (not torch.is_tensor(o) or o.dtype != torch.int64 or o.dim() != 1 or o.device != a.device):
+            raise ValueError(f"{what}: {oname} must be a 1-D int64 tensor on the keys' device")
+    if a_offsets is not None and a_offsets.numel() != b_offsets.numel():
+        raise ValueError(f"{what}: a_offsets and b_offsets must have the same number of entries")
+    if capacity is not None and (not isinstance(capacity, int) or isinstance(capacity, bool) or capacity < 0 or capacity > (1 << 34)):
+        raise ValueError(f"{what}: capacity must be None or an int in [0, 2^34]")
+    na, nb = a.numel(), b.numel()
+    if na > (1 << 31) or nb > (1 << 31):
+        raise ValueError(f"{what}: at most 2^31 keys in a and in b (rsx_segmented_join's bound)")
+    nseg = 1 if a_offsets is None else max(a_offsets.numel() - 1, 0)
+    dev = a.device
+    ooff = torch.zeros(nseg + 1, dtype=torch.int64, device=dev)
+    want_b = code != JOIN_ANTI
+    eng = None
+    if nseg > 0:
+        a_in, b_in = _aligned_copy(a, torch), _aligned_copy(b, torch)
+        cont = lambda t: None if t is None else t if t.is_contiguous() and t.data_ptr() % 8 == 0 else t.clone(memory_format=torch.contiguous_format)
+        ao, bo = cont(a_offsets), cont(b_offsets)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        device = dev.index if dev.index is not None else torch.cuda.current_device()
+        eng = _search_engine(device, torch.cuda.current_stream(dev).cuda_stream, name, bool(descending))
+        join = lambda cap, ko, io, bo_: eng.segmented_join(ptr(a_in), na, ptr(ao), ptr(b_in), nb, ptr(bo), nseg, code, cap, ooff.data_ptr(),
+                                                           d_a_index_out=ptr(io), d_b_index_out=ptr(bo_), d_keys_out=ptr(ko))
+    if capacity is None:
+        cap = 0
+        if eng is not None:
+            join(0, None, None, None)
+            cap = int(ooff[-1].item())          # the one read-back (a host synchronisation): how many rows there are
+            eng.check_status()
+            if cap > (1 << 34):
+                raise ValueError(f"{what}: {cap} rows are more than one call writes (2^34); join in pieces, or pass capacity")
+    else:
+        cap = capacity
+    # (uint32 results in int32 storage: "none" is -1 as it stands, and the buffers of capacity=int start out as -1)
+    ia = torch.full((cap,), -1, dtype=torch.int32, device=dev)
+    ib = torch.full((cap,), -1, dtype=torch.int32, device=dev) if want_b else None
+    keys = torch.zeros(cap, dtype=a.dtype, device=dev) if want_keys else None
+    if eng is not None and cap > 0:
+        join(cap, keys, ia, ib)
+        eng.check_status()      # reports bad offsets of calls that have already finished; no synchronisation
+    widen = lambda t: None if t is None else torch.where(t == -1, t.to(torch.int64), t.to(torch.int64) & 0xFFFFFFFF)
+    return widen(ia), widen(ib), ooff, keys
+
+
+def segmented_join(a, a_offsets, b, b_offsets, how="inner", descending: bool = False, return_keys: bool = False, capacity=None):
+    """The equi-join of sorted segment a[a_offsets[s] : a_offsets[s+1]] with sorted segment b[b_offsets[s] : b_offsets[s+1]], for every s, in
+    rsx_segmented_join: returns (ia, ib, out_offsets[, keys]).  how: "inner" (every a element with every equal b element: a key that occurs
+    m times in a's segment and n times in b's gives m x n rows), "left" (the same, and one row with ib = -1 for an a element without a
+    partner), "semi" (one row per a element that has a partner, ib its first), "anti" (one row per a element that has none; ib is None), or
+    the JOIN_* constants.  ia and ib (int64) are positions relative to the segments' starts; rows out_offsets[s] : out_offsets[s+1] belong
+    to segment s, ordered by ia, then ib.  keys (return_keys): a's key of every row.  Keys are equal iff their bits are (-0.0 and +0.0 do
+    not join; NaNs with equal bits do).  The segments must be sorted as this library sorts them (segmented_sort / sort_rows with the same
+    `descending`); inputs that are not sorted give unspecified rows.  capacity=None counts first, reads the total back (ONE host
+    synchronisation) and returns exactly the rows.  capacity=int never synchronises: the buffers have that length, hold -1 (keys: 0) behind
+    min(out_offsets[-1], capacity), and the caller compares out_offsets[-1] with capacity.  Bad offsets raise RadixSortError."""
+    ia, ib, oo, k = _join_call("segmented_join", a, a_offsets, b, b_offsets, how, descending, return_keys, capacity)
+    return (ia, ib, oo) + ((k,) if return_keys else ())
+
+
+def _join_rows(what: str, a, b):
+    import torch
+    for name, t in (("a", a), ("b", b)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{what}: {name} must be a tensor")
+    if a.dim() == 0 or a.dim() != b.dim() or tuple(a.shape[:-1]) != tuple(b.shape[:-1]):
+        raise ValueError(f"{what}: a and b must have the same number of dimensions (at least one) and equal leading shape")
+    la, lb = a.shape[-1], b.shape[-1]
+    ao = bo = None
+    if a.dim() > 1:
+        rows = a.numel() // la if la else (b.numel() // lb if lb else 0)
+        steps = torch.arange(0, rows + 1, device=a.device, dtype=torch.int64)
+        ao, bo = steps * la, steps * lb
+    return a.contiguous().reshape(-1), ao, b.contiguous().reshape(-1), bo
+
+
+def join_sorted(a, b, how="inner", descending: bool = False, capacity=None):
+    """The equi-join of two sorted device tensors along their last dimension.  1-D inputs are one segment: (ia, ib) comes back, the
+    positions in a and in b of every pair of equal keys (a[ia] == b[ib] bit for bit), ordered by ia, then ib.  N-D inputs with equal
+    leading shape are joined row by row, the rows being the segments of one rsx_segmented_join, and (ia, ib, row_offsets) comes back:
+    ia and ib are columns, and row r's pairs are [row_offsets[r] : row_offsets[r+1]).  how, capacity, order and errors as
+    segmented_join."""
+    fa, ao, fb, bo = _join_rows("join_sorted", a, b)
+    ia, ib, oo, _ = _join_call("join_sorted", fa, ao, fb, bo, how, descending, False, capacity)
+    return (ia, ib) + ((oo,) if a.dim() > 1 else ())
+
+
+def isin_sorted(a, b, invert: bool = False, descending: bool = False):
+    """torch.isin(a, b) for sorted device tensors, by bits: a bool tensor shaped like a, True where the element has an equal element in b
+    (in b's row of the same index for N-D inputs); invert=True: where it has none.  The semi (anti) join scattered to a mask; never
+    synchronises with the host."""
+    import torch
+    fa, ao, fb, bo = _join_rows("isin_sorted", a, b)
+    na = fa.numel() if torch.is_tensor(fa) else 0
+    ia, _, oo, _ = _join_call("isin_sorted", fa, ao, fb, bo, JOIN_ANTI if invert else JOIN_SEMI, descending, False, na)
+    mask = torch.zeros(na + 1, dtype=torch.bool, device=fa.device)
+    if ao is not None and na:
+        # columns -> flat positions: row r's rows are [oo[r], oo[r+1]); rows behind the total hold -1 and land in the spare slot
+        row = torch.searchsorted(oo[1:].contiguous(), torch.arange(na, device=fa.device), right=True).clamp_(max=ao.numel() - 2)
+        ia = torch.where(ia >= 0, ia + ao[row], ia)
+    mask.index_fill_(0, torch.where(ia < 0, na, ia), True)          # (rows behind the total go to the spare last slot; no host value, no synchronisation)
+    return mask[:na].reshape(a.shape)

@@ -1,4 +1,4 @@
-// capi_family.inc — the host front end that the thirteen segmented calls share (capi_segmented.inc ... capi_expand.inc): the buffer rules, the
+// capi_family.inc — the host front end that the fourteen segmented calls share (capi_segmented.inc ... capi_join.inc): the buffer rules, the
 // 32/64-bit dispatch, the engine state after a call, the scratch that grows on demand, the tile arithmetic, the check of the offsets and
 // the table scan.  No kernel of its own: every launch in here is one that each call used to spell out itself.  The address arithmetic
 // is in rsx_args.hpp.  Included by rsx_capi.hip first inside its extern "C" block (templates and helpers: C++ linkage).

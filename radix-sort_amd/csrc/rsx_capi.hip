@@ -23,6 +23,7 @@
 #include "rsx_compact.hpp"
 #include "rsx_merge.hpp"
 #include "rsx_setop.hpp"
+#include "rsx_join.hpp"
 #include "rsx_bins.hpp"
 #include "rsx_args.hpp"
 
@@ -240,6 +241,18 @@ struct rsx_engine {
     // rsx_segmented_expand (capi_expand.inc): the number of offsets below every tile boundary of the absolute output grid
     uint32_t* expand_split = nullptr;
     uint64_t expand_split_cap = 0;
+    // rsx_segmented_join (capi_join.inc): per A position the in-tile row prefix, the first partner and the position inside its segment; per
+    // A tile the rows before it; per boundary of the output grid the A positions below it
+    uint64_t* join_pre = nullptr;
+    uint64_t join_pre_cap = 0;
+    uint64_t* join_tbase = nullptr;
+    uint64_t join_tbase_cap = 0;
+    uint32_t* join_first = nullptr;
+    uint64_t join_first_cap = 0;
+    uint32_t* join_arel = nullptr;
+    uint64_t join_arel_cap = 0;
+    uint32_t* join_split = nullptr;
+    uint64_t join_split_cap = 0;
 
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -1261,6 +1274,7 @@ constexpr uint32_t kStatusCallSetop = 2;
 constexpr uint32_t kStatusCallHistogram = 3;
 constexpr uint32_t kStatusCallReduce = 4;
 constexpr uint32_t kStatusCallExpand = 5;
+constexpr uint32_t kStatusCallJoin = 6;
 int check_scan_timeout(rsx_engine* e, int status)
 {
     if (e->seg_status_host) {
@@ -1289,6 +1303,10 @@ int check_scan_timeout(rsx_engine* e, int status)
                 return fail(status, ("rsx_segmented_expand: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n, or in gather form "
                                      "starts[s] + its length > num_values; nothing was written (the first such segment of the call; reported once; the "
                                      "engine remains usable)").c_str());
+            if (call == kStatusCallJoin)
+                return fail(status, ("rsx_segmented_join: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n in d_a_offsets (n = na) or in "
+                                     "d_b_offsets (n = nb); d_out_offsets holds zeros and nothing else was written (the first such segment of the call; "
+                                     "reported once; the engine remains usable)").c_str());
             return fail(status, ("rsx_segmented_sort / rsx_segmented_topk / rsx_segmented_select: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; it was neither read nor "
                                  "written (the first such segment of the call; reported once; the engine remains usable)").c_str());
         }
@@ -1658,7 +1676,8 @@ int rsx_destroy(rsx_engine* e)
                     static_cast<void*>(e->seg_large), static_cast<void*>(e->seg_tstart), static_cast<void*>(e->seg_table), static_cast<void*>(e->seg_gsum),
                     static_cast<void*>(e->seg_gsum2), static_cast<void*>(e->topk_state), static_cast<void*>(e->topk_start),
                     static_cast<void*>(e->topk_cont), static_cast<void*>(e->uniq_iota), static_cast<void*>(e->red_part), static_cast<void*>(e->merge_split),
-                    static_cast<void*>(e->expand_split)}) {
+                    static_cast<void*>(e->expand_split), static_cast<void*>(e->join_pre), static_cast<void*>(e->join_tbase),
+                    static_cast<void*>(e->join_first), static_cast<void*>(e->join_arel), static_cast<void*>(e->join_split)}) {
         if (p && hipFree(p) != hipSuccess) status = RSX_CLEANUP_FAILED;
     }
     if (e->seg_status_host && hipHostFree(e->seg_status_host) != hipSuccess) status = RSX_CLEANUP_FAILED;
@@ -2420,6 +2439,7 @@ int rsx_peer_enable(rsx_engine* e, int peer_device)
 #include "capi_histogram.inc"
 #include "capi_segreduce.inc"
 #include "capi_expand.inc"
+#include "capi_join.inc"
 
 int rsx_key_range(rsx_engine* e, const void* d_keys, uint64_t n, uint64_t* lo, uint64_t* hi)
 {
