@@ -20,6 +20,8 @@ import sys
 
 import numpy as np
 
+from . import _tensor_args as _args
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RSX_LIB") or os.path.join(_HERE, "libradixsort_hip.so")   # RSX_LIB: A/B builds while tuning
 
@@ -240,9 +242,12 @@ def device_name(device: int = 0) -> str:
     return buf.value.decode()
 
 
-# dtype name -> (key bytes, key kind)
-_KEY_DTYPES = {"uint32": (4, KEY_UNSIGNED), "int32": (4, KEY_SIGNED), "uint64": (8, KEY_UNSIGNED), "int64": (8, KEY_SIGNED),
-               "float32": (4, KEY_FLOAT), "float64": (8, KEY_FLOAT)}
+_KEY_DTYPES = _args.KEY_DTYPES      # dtype name -> (key bytes, key kind)
+
+
+def _opt(p):
+    """an optional device address as ctypes wants it: NULL for None and 0"""
+    return C.c_void_p(p) if p else None
 
 
 class Engine:
@@ -390,14 +395,14 @@ class Engine:
 
     # -- device-resident callers ----------------------------------------------
     def sort_from(self, d_keys: int, n: int, d_payload: int | None = None) -> None:
-        self._check(self.lib.rsx_sort_from(self._h, C.c_void_p(d_keys), C.c_void_p(d_payload) if d_payload else None, n), "rsx_sort_from")
+        self._check(self.lib.rsx_sort_from(self._h, C.c_void_p(d_keys), _opt(d_payload), n), "rsx_sort_from")
 
     def partition(self, d_keys: int, n: int, shift: int, bits: int, d_keys_out: int,
                   d_payload: int | None = None, d_payload_out: int | None = None) -> list[int]:
         offs = (C.c_uint64 * ((1 << bits) + 1))()
         self._check(self.lib.rsx_partition(
-            self._h, C.c_void_p(d_keys), C.c_void_p(d_payload) if d_payload else None, n, shift, bits,
-            C.c_void_p(d_keys_out), C.c_void_p(d_payload_out) if d_payload_out else None, offs), "rsx_partition")
+            self._h, C.c_void_p(d_keys), _opt(d_payload), n, shift, bits,
+            C.c_void_p(d_keys_out), _opt(d_payload_out), offs), "rsx_partition")
         return [int(v) for v in offs]
 
     def partition_count(self, d_keys: int, n: int, shift: int, bits: int) -> list[int]:
@@ -408,8 +413,8 @@ class Engine:
     def partition_scatter(self, d_keys: int, n: int, shift: int, bits: int, d_keys_out: int,
                           d_payload: int | None = None, d_payload_out: int | None = None) -> None:
         self._check(self.lib.rsx_partition_scatter(
-            self._h, C.c_void_p(d_keys), C.c_void_p(d_payload) if d_payload else None, n, shift, bits,
-            C.c_void_p(d_keys_out), C.c_void_p(d_payload_out) if d_payload_out else None), "rsx_partition_scatter")
+            self._h, C.c_void_p(d_keys), _opt(d_payload), n, shift, bits,
+            C.c_void_p(d_keys_out), _opt(d_payload_out)), "rsx_partition_scatter")
 
     def sample_keys(self, d_keys: int, n: int, count: int) -> list[int]:
         out = (C.c_uint64 * count)()
@@ -425,8 +430,8 @@ class Engine:
 
     def partition_scatter_split(self, d_keys: int, n: int, d_keys_out: int, d_payload: int | None = None, d_payload_out: int | None = None) -> None:
         self._check(self.lib.rsx_partition_scatter_split(
-            self._h, C.c_void_p(d_keys), C.c_void_p(d_payload) if d_payload else None, n,
-            C.c_void_p(d_keys_out), C.c_void_p(d_payload_out) if d_payload_out else None), "rsx_partition_scatter_split")
+            self._h, C.c_void_p(d_keys), _opt(d_payload), n,
+            C.c_void_p(d_keys_out), _opt(d_payload_out)), "rsx_partition_scatter_split")
 
     def peer_alloc(self, nbytes: int) -> tuple[int, bytes]:
         """A device buffer other ranks may write to: (address, IPC handle for other processes)."""
@@ -452,8 +457,8 @@ class Engine:
                      d_payload: int | None = None, d_payload_out: int | None = None) -> None:
         """Device-to-device sort over passes [first_pass, last_pass); the last pass writes to d_keys_out."""
         self._check(self.lib.rsx_sort_from_to(
-            self._h, C.c_void_p(d_keys), C.c_void_p(d_payload) if d_payload else None, n, first_pass, last_pass,
-            C.c_void_p(d_keys_out), C.c_void_p(d_payload_out) if d_payload_out else None), "rsx_sort_from_to")
+            self._h, C.c_void_p(d_keys), _opt(d_payload), n, first_pass, last_pass,
+            C.c_void_p(d_keys_out), _opt(d_payload_out)), "rsx_sort_from_to")
 
     def segmented_sort(self, d_keys: int, n: int, d_offsets: int, num_segments: int, d_keys_out: int,
                        d_payload: int | None = None, d_payload_out: int | None = None) -> None:
@@ -461,8 +466,8 @@ class Engine:
         num_segments + 1 uint64 / non-negative int64), asynchronously on the engine's stream.  Bad offsets are reported by the
         next sync() / check_status()."""
         self._check(self.lib.rsx_segmented_sort(
-            self._h, C.c_void_p(d_keys), C.c_void_p(d_payload) if d_payload else None, n, C.c_void_p(d_offsets), num_segments,
-            C.c_void_p(d_keys_out), C.c_void_p(d_payload_out) if d_payload_out else None), "rsx_segmented_sort")
+            self._h, C.c_void_p(d_keys), _opt(d_payload), n, C.c_void_p(d_offsets), num_segments,
+            C.c_void_p(d_keys_out), _opt(d_payload_out)), "rsx_segmented_sort")
 
     def segmented_topk(self, d_keys: int, n: int, d_offsets: int, num_segments: int, k: int, d_keys_out: int, d_index_out: int) -> None:
         """The first min(k, L) entries of the stable sort of every segment [off[s], off[s+1]) (L keys) to d_keys_out[s*k ..] and their
@@ -490,9 +495,9 @@ class Engine:
         inverse map (n uint32 each).  d_offsets None: ONE segment [0, n).  First positions / the inverse map of a sorted call need a payload
         engine.  Asynchronous on the engine's stream; bad offsets are reported by the next sync() / check_status()."""
         self._check(self.lib.rsx_segmented_unique(
-            self._h, C.c_void_p(d_keys), n, C.c_void_p(d_offsets) if d_offsets else None, num_segments, UNIQUE_CONSECUTIVE if consecutive else 0,
-            C.c_void_p(d_keys_out), C.c_void_p(d_run_offsets_out), C.c_void_p(d_counts_out) if d_counts_out else None,
-            C.c_void_p(d_first_out) if d_first_out else None, C.c_void_p(d_inverse_out) if d_inverse_out else None), "rsx_segmented_unique")
+            self._h, C.c_void_p(d_keys), n, _opt(d_offsets), num_segments, UNIQUE_CONSECUTIVE if consecutive else 0,
+            C.c_void_p(d_keys_out), C.c_void_p(d_run_offsets_out), _opt(d_counts_out),
+            _opt(d_first_out), _opt(d_inverse_out)), "rsx_segmented_unique")
 
     def segmented_reduce_by_key(self, d_keys: int, d_values: int, n: int, d_offsets: int | None, num_segments: int, op: int, value_kind: int,
                                 d_keys_out: int, d_run_offsets_out: int, d_values_out: int, d_counts_out: int | None = None,
@@ -504,9 +509,9 @@ class Engine:
         A sorted call needs a payload engine.  Asynchronous on the engine's stream; bad offsets are reported by the next sync() /
         check_status()."""
         self._check(self.lib.rsx_segmented_reduce_by_key(
-            self._h, C.c_void_p(d_keys), C.c_void_p(d_values), n, C.c_void_p(d_offsets) if d_offsets else None, num_segments,
+            self._h, C.c_void_p(d_keys), C.c_void_p(d_values), n, _opt(d_offsets), num_segments,
             UNIQUE_CONSECUTIVE if consecutive else 0, op, value_kind, C.c_void_p(d_keys_out), C.c_void_p(d_run_offsets_out),
-            C.c_void_p(d_values_out), C.c_void_p(d_counts_out) if d_counts_out else None), "rsx_segmented_reduce_by_key")
+            C.c_void_p(d_values_out), _opt(d_counts_out)), "rsx_segmented_reduce_by_key")
 
     def segmented_scan(self, d_keys: int | None, d_values: int, n: int, d_offsets: int | None, num_segments: int, op: int, value_kind: int,
                        d_values_out: int, exclusive: bool = False) -> None:
@@ -517,7 +522,7 @@ class Engine:
         result is left alone.  Asynchronous on the engine's stream; bad offsets (nothing is written then) are reported by the next
         sync() / check_status()."""
         self._check(self.lib.rsx_segmented_scan(
-            self._h, C.c_void_p(d_keys) if d_keys else None, C.c_void_p(d_values), n, C.c_void_p(d_offsets) if d_offsets else None, num_segments,
+            self._h, _opt(d_keys), C.c_void_p(d_values), n, _opt(d_offsets), num_segments,
             SCAN_EXCLUSIVE if exclusive else 0, op, value_kind, C.c_void_p(d_values_out)), "rsx_segmented_scan")
 
     def segmented_reduce(self, d_values: int | None, n: int, d_offsets: int | None, num_segments: int, op: int, value_kind: int,
@@ -529,8 +534,8 @@ class Engine:
         bits.  n may exceed the capacity and the engine's sort result is left alone.  Asynchronous on the engine's stream; bad offsets
         (nothing is written then) are reported by the next sync() / check_status()."""
         self._check(self.lib.rsx_segmented_reduce(
-            self._h, C.c_void_p(d_values) if d_values else None, n, C.c_void_p(d_offsets) if d_offsets else None, num_segments, 0, op, value_kind,
-            C.c_void_p(d_values_out) if d_values_out else None, C.c_void_p(d_index_out) if d_index_out else None), "rsx_segmented_reduce")
+            self._h, _opt(d_values), n, _opt(d_offsets), num_segments, 0, op, value_kind,
+            _opt(d_values_out), _opt(d_index_out)), "rsx_segmented_reduce")
 
     def segmented_expand(self, d_values: int | None, num_values: int, value_bytes: int, d_offsets: int | None, num_segments: int, n: int,
                          d_starts: int | None = None, d_values_out: int | None = None, d_segment_out: int | None = None,
@@ -543,9 +548,9 @@ class Engine:
         exceed the capacity and the engine's sort result is left alone.  Asynchronous on the engine's stream; bad offsets or starts
         (nothing is written then) are reported by the next sync() / check_status()."""
         self._check(self.lib.rsx_segmented_expand(
-            self._h, C.c_void_p(d_values) if d_values else None, num_values, value_bytes, C.c_void_p(d_offsets) if d_offsets else None, num_segments, n,
-            C.c_void_p(d_starts) if d_starts else None, EXPAND_GATHER if d_starts else 0, C.c_void_p(d_values_out) if d_values_out else None,
-            C.c_void_p(d_segment_out) if d_segment_out else None, C.c_void_p(d_rank_out) if d_rank_out else None), "rsx_segmented_expand")
+            self._h, _opt(d_values), num_values, value_bytes, _opt(d_offsets), num_segments, n,
+            _opt(d_starts), EXPAND_GATHER if d_starts else 0, _opt(d_values_out),
+            _opt(d_segment_out), _opt(d_rank_out)), "rsx_segmented_expand")
 
     def segmented_search(self, d_sorted: int | None, n: int, d_offsets: int | None, num_segments: int, d_queries: int, num_queries: int,
                          d_query_offsets: int | None, d_index_out: int, right: bool = False) -> None:
@@ -556,9 +561,9 @@ class Engine:
         [qoff[s], qoff[s+1]).  n may exceed the capacity and the engine's sort result is left alone.  Asynchronous on the engine's stream;
         bad offsets (nothing is written then) are reported by the next sync() / check_status()."""
         self._check(self.lib.rsx_segmented_search(
-            self._h, C.c_void_p(d_sorted) if d_sorted else None, n, C.c_void_p(d_offsets) if d_offsets else None, num_segments,
-            C.c_void_p(d_queries) if d_queries else None, num_queries, C.c_void_p(d_query_offsets) if d_query_offsets else None,
-            SEARCH_RIGHT if right else 0, C.c_void_p(d_index_out) if d_index_out else None), "rsx_segmented_search")
+            self._h, _opt(d_sorted), n, _opt(d_offsets), num_segments,
+            _opt(d_queries), num_queries, _opt(d_query_offsets),
+            SEARCH_RIGHT if right else 0, _opt(d_index_out)), "rsx_segmented_search")
 
     def segmented_compact(self, d_keys: int, n: int, d_offsets: int | None, num_segments: int, d_mask: int | None, d_bounds: int | None,
                           d_keys_out: int | None, d_index_out: int | None, d_kept_offsets_out: int, partition: bool = False, invert: bool = False,
@@ -572,10 +577,9 @@ class Engine:
         sort result is left alone.  Asynchronous on the engine's stream; bad offsets (the kept offsets are zeros then, nothing else is
         written) are reported by the next sync() / check_status()."""
         flags = (COMPACT_PARTITION if partition else 0) | (COMPACT_INVERT if invert else 0) | (COMPACT_STRICT if strict else 0)
-        opt = lambda p: C.c_void_p(p) if p else None
         self._check(self.lib.rsx_segmented_compact(
-            self._h, opt(d_keys), n, opt(d_offsets), num_segments, opt(d_mask), opt(d_bounds), flags, opt(d_keys_out), opt(d_index_out),
-            opt(d_kept_offsets_out)), "rsx_segmented_compact")
+            self._h, _opt(d_keys), n, _opt(d_offsets), num_segments, _opt(d_mask), _opt(d_bounds), flags, _opt(d_keys_out), _opt(d_index_out),
+            _opt(d_kept_offsets_out)), "rsx_segmented_compact")
 
     def segmented_merge(self, d_a: int | None, na: int, d_a_offsets: int | None, d_b: int | None, nb: int, d_b_offsets: int | None, num_segments: int,
                         d_keys_out: int | None, d_index_out: int | None = None, d_out_offsets: int | None = None, d_a_payload: int | None = None,
@@ -588,10 +592,9 @@ class Engine:
         engine's order (key kind, totalOrder for floats, direction).  Each output may be None, not all.  na + nb may exceed the capacity,
         the engine's sort result is left alone, and has_payload does not matter.  Asynchronous on the engine's stream; bad offsets
         (d_out_offsets holds zeros then, nothing else is written) are reported by the next sync() / check_status()."""
-        opt = lambda p: C.c_void_p(p) if p else None
         self._check(self.lib.rsx_segmented_merge(
-            self._h, opt(d_a), opt(d_a_payload), na, opt(d_a_offsets), opt(d_b), opt(d_b_payload), nb, opt(d_b_offsets), num_segments, flags,
-            opt(d_keys_out), opt(d_payload_out), opt(d_index_out), opt(d_out_offsets)), "rsx_segmented_merge")
+            self._h, _opt(d_a), _opt(d_a_payload), na, _opt(d_a_offsets), _opt(d_b), _opt(d_b_payload), nb, _opt(d_b_offsets), num_segments, flags,
+            _opt(d_keys_out), _opt(d_payload_out), _opt(d_index_out), _opt(d_out_offsets)), "rsx_segmented_merge")
 
     def segmented_set_op(self, d_a: int | None, na: int, d_a_offsets: int | None, d_b: int | None, nb: int, d_b_offsets: int | None, num_segments: int,
                          op: int, d_keys_out: int | None, d_out_offsets: int | None, d_index_out: int | None = None, d_match_out: int | None = None,
@@ -606,10 +609,9 @@ class Engine:
         for intersection and difference, na + nb for the other two.  Both offsets None: ONE segment.  na + nb may exceed the capacity, the
         engine's sort result is left alone, and has_payload does not matter.  Asynchronous on the engine's stream; bad offsets
         (d_out_offsets holds zeros then, nothing else is written) are reported by the next sync() / check_status()."""
-        opt = lambda p: C.c_void_p(p) if p else None
         self._check(self.lib.rsx_segmented_set_op(
-            self._h, opt(d_a), opt(d_a_payload), na, opt(d_a_offsets), opt(d_b), opt(d_b_payload), nb, opt(d_b_offsets), num_segments, op, flags,
-            opt(d_keys_out), opt(d_payload_out), opt(d_index_out), opt(d_match_out), opt(d_out_offsets)), "rsx_segmented_set_op")
+            self._h, _opt(d_a), _opt(d_a_payload), na, _opt(d_a_offsets), _opt(d_b), _opt(d_b_payload), nb, _opt(d_b_offsets), num_segments, op, flags,
+            _opt(d_keys_out), _opt(d_payload_out), _opt(d_index_out), _opt(d_match_out), _opt(d_out_offsets)), "rsx_segmented_set_op")
 
     def segmented_join(self, d_a: int | None, na: int, d_a_offsets: int | None, d_b: int | None, nb: int, d_b_offsets: int | None, num_segments: int,
                        op: int, out_capacity: int, d_out_offsets: int | None, d_a_index_out: int | None = None, d_b_index_out: int | None = None,
@@ -624,10 +626,9 @@ class Engine:
         nb and the total may exceed the capacity, the engine's sort result is left alone, and has_payload does not matter.  Asynchronous
         on the engine's stream; bad offsets (d_out_offsets holds zeros then, nothing else is written) are reported by the next sync() /
         check_status()."""
-        opt = lambda p: C.c_void_p(p) if p else None
         self._check(self.lib.rsx_segmented_join(
-            self._h, opt(d_a), na, opt(d_a_offsets), opt(d_b), nb, opt(d_b_offsets), num_segments, op, flags, out_capacity,
-            opt(d_keys_out), opt(d_a_index_out), opt(d_b_index_out), opt(d_out_offsets)), "rsx_segmented_join")
+            self._h, _opt(d_a), na, _opt(d_a_offsets), _opt(d_b), nb, _opt(d_b_offsets), num_segments, op, flags, out_capacity,
+            _opt(d_keys_out), _opt(d_a_index_out), _opt(d_b_index_out), _opt(d_out_offsets)), "rsx_segmented_join")
 
     def key_bits(self, value) -> int:
         """The bit pattern of the Python number `value` as a key of this engine (two's complement for integers, IEEE 754 for floats)."""
@@ -645,11 +646,10 @@ class Engine:
         numbers.  A descending engine numbers the even forms' bins backwards.  d_offsets None: ONE segment [0, n).  n may exceed the
         capacity and the engine's sort result is left alone.  Asynchronous on the engine's stream; bad offsets (every counter is zero
         then) are reported by the next sync() / check_status()."""
-        opt = lambda p: C.c_void_p(p) if p else None
         even = not d_edges
         self._check(self.lib.rsx_segmented_histogram(
-            self._h, opt(d_keys), n, opt(d_offsets), num_segments, opt(d_edges), self.key_bits(lo) if even else int(lo),
-            self.key_bits(hi) if even else int(hi), width_shift, num_bins, 0, opt(d_counts_out)), "rsx_segmented_histogram")
+            self._h, _opt(d_keys), n, _opt(d_offsets), num_segments, _opt(d_edges), self.key_bits(lo) if even else int(lo),
+            self.key_bits(hi) if even else int(hi), width_shift, num_bins, 0, _opt(d_counts_out)), "rsx_segmented_histogram")
 
     # -- exchange step of the sharded sort on the top B <= 8 bits ----------------
     def msd_count(self, d_keys: int, n: int, bits: int, world: int, d_counts: int) -> None:
@@ -657,11 +657,11 @@ class Engine:
         self._check(self.lib.rsx_msd_count(self._h, C.c_void_p(d_keys), n, bits, world, C.c_void_p(d_counts)), "rsx_msd_count")
 
     def msd_scatter(self, d_keys: int, n: int, d_staging: int, d_payload: int | None = None, d_staging_payload: int | None = None) -> None:
-        self._check(self.lib.rsx_msd_scatter(self._h, C.c_void_p(d_keys), C.c_void_p(d_payload) if d_payload else None, n, C.c_void_p(d_staging),
-                                             C.c_void_p(d_staging_payload) if d_staging_payload else None), "rsx_msd_scatter")
+        self._check(self.lib.rsx_msd_scatter(self._h, C.c_void_p(d_keys), _opt(d_payload), n, C.c_void_p(d_staging),
+                                             _opt(d_staging_payload)), "rsx_msd_scatter")
 
     def msd_plan(self, d_table: int, stride: int, cap_at: int, rank: int, hip_stream: int = 0, grouping: int = 0) -> None:
-        self._check(self.lib.rsx_msd_plan(self._h, C.c_void_p(d_table), stride, cap_at, rank, grouping, C.c_void_p(hip_stream) if hip_stream else None), "rsx_msd_plan")
+        self._check(self.lib.rsx_msd_plan(self._h, C.c_void_p(d_table), stride, cap_at, rank, grouping, _opt(hip_stream)), "rsx_msd_plan")
 
     def msd_plan_wait(self, waves: int, world: int) -> tuple[list[int], list[int], list[int], int]:
         """(first slot of every wave in this rank's receive buffer, keys of every wave, keys every rank ends up with, verdict bits)"""
@@ -672,9 +672,9 @@ class Engine:
     def msd_push(self, wave: int, d_staging: int, d_peer_keys: int, d_staging_payload: int | None = None, d_peer_payload: int | None = None, parts: int = 0,
                  hip_stream: int = 0) -> None:
         """Wave `wave` of the staging buffer into the owners' receive buffers, on hip_stream (0: the engine's stream)."""
-        self._check(self.lib.rsx_msd_push(self._h, wave, C.c_void_p(d_staging), C.c_void_p(d_staging_payload) if d_staging_payload else None,
-                                          C.c_void_p(d_peer_keys), C.c_void_p(d_peer_payload) if d_peer_payload else None, parts,
-                                          C.c_void_p(hip_stream) if hip_stream else None), "rsx_msd_push")
+        self._check(self.lib.rsx_msd_push(self._h, wave, C.c_void_p(d_staging), _opt(d_staging_payload),
+                                          C.c_void_p(d_peer_keys), _opt(d_peer_payload), parts,
+                                          _opt(hip_stream)), "rsx_msd_push")
 
     def wait_for(self, other: "Engine") -> None:
         """This engine's stream waits for everything enqueued on `other`'s stream so far."""
@@ -697,8 +697,8 @@ class Engine:
                         d_payload: int | None = None, d_payload_out: int | None = None) -> list[int]:
         offs = (C.c_uint64 * 17)()
         self._check(self.lib.rsx_partition_range(
-            self._h, C.c_void_p(d_keys), C.c_void_p(d_payload) if d_payload else None, n, lo, shift, mul,
-            C.c_void_p(d_keys_out), C.c_void_p(d_payload_out) if d_payload_out else None, offs), "rsx_partition_range")
+            self._h, C.c_void_p(d_keys), _opt(d_payload), n, lo, shift, mul,
+            C.c_void_p(d_keys_out), _opt(d_payload_out), offs), "rsx_partition_range")
         return [int(v) for v in offs]
 
     def result_device(self) -> tuple[int, int]:
@@ -707,7 +707,7 @@ class Engine:
         return int(k.value or 0), int(p.value or 0)
 
     def copy_result(self, d_keys_out: int, d_payload_out: int | None = None) -> None:
-        self._check(self.lib.rsx_copy_result(self._h, C.c_void_p(d_keys_out), C.c_void_p(d_payload_out) if d_payload_out else None), "rsx_copy_result")
+        self._check(self.lib.rsx_copy_result(self._h, C.c_void_p(d_keys_out), _opt(d_payload_out)), "rsx_copy_result")
 
     def timings(self, reset: bool = False) -> Runtimes:
         r = Runtimes()
@@ -747,25 +747,37 @@ def sort_host(keys: np.ndarray, payload: np.ndarray | None = None, device: int =
 _SEG_ENGINES: dict = {}
 
 
-def _segmented_engine(device: int, stream: int, dtype_name: str, payload: bool, descending: bool, n: int) -> "Engine":
-    key = (device, stream, dtype_name, payload, descending)
-    eng = _SEG_ENGINES.get(key)
-    if eng is None or eng.capacity < n:
-        if eng is not None:
-            eng.close()
-        cap = max(n, 1 << 12)
-        cap = 1 << (cap - 1).bit_length() if cap < (1 << 31) else cap
-        eng = Engine(dtype_name, cap, payload=payload, device=device, descending=descending)
-        eng.set_stream(stream)
-        _SEG_ENGINES[key] = eng
+def _cached_engine(cache: dict, key: tuple, dtype_name: str, capacity: int, payload: bool = False, descending: bool = False) -> "Engine":
+    """The engine of a cache under `key` = (device, stream, ...), created on that device and bound to that stream on first use."""
+    eng = cache.get(key)
+    if eng is None:
+        eng = Engine(dtype_name, capacity, payload=payload, device=key[0], descending=descending)
+        eng.set_stream(key[1])
+        cache[key] = eng
     return eng
 
 
-def _aligned_copy(t, torch):
-    """t itself when contiguous and 16-byte aligned, else a fresh contiguous copy (torch allocations are aligned)."""
-    if t.is_contiguous() and t.data_ptr() % 16 == 0:
-        return t
-    return t.clone(memory_format=torch.contiguous_format)
+def _segmented_engine(device: int, stream: int, dtype_name: str, payload: bool, descending: bool, n: int) -> "Engine":
+    key = (device, stream, dtype_name, payload, descending)
+    eng = _SEG_ENGINES.get(key)
+    if eng is not None and eng.capacity < n:          # too small: replaced by one of the next power of two
+        eng.close()
+        del _SEG_ENGINES[key]
+    cap = max(n, 1 << 12)
+    cap = 1 << (cap - 1).bit_length() if cap < (1 << 31) else cap
+    return _cached_engine(_SEG_ENGINES, key, dtype_name, cap, payload, descending)
+
+
+_aligned_copy = _args.aligned_copy
+
+
+def _keys_and_offsets(what: str, keys, offsets) -> str:
+    """What sort, topk and select ask of their input: 1-D device keys of a key type (its name) and offsets on their device."""
+    if keys.dim() != 1 or not keys.is_cuda:
+        raise ValueError(f"{what}: keys must be a 1-D device tensor")
+    name = _args.key_name(what, keys)
+    _args.check_offsets(what, offsets, keys.device)
+    return name
 
 
 def segmented_sort(keys, offsets, payload=None, descending: bool = False):
@@ -774,31 +786,22 @@ def segmented_sort(keys, offsets, payload=None, descending: bool = False):
     Returns new (keys, payload) tensors (payload None without one); positions outside [offsets[0], offsets[-1]) are copied unchanged.
     Float keys sort in IEEE 754 totalOrder.  Bad offsets raise at the engine's next synchronisation (this call does not read them)."""
     import torch
-    if keys.dim() != 1 or not keys.is_cuda:
-        raise ValueError("segmented_sort: keys must be a 1-D device tensor")
-    name = str(keys.dtype).replace("torch.", "")
-    if name not in _KEY_DTYPES:
-        raise TypeError(f"segmented_sort: unsupported key type {keys.dtype}")
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.device != keys.device:
-        raise ValueError("segmented_sort: offsets must be a 1-D int64 tensor on the keys' device")
+    name = _keys_and_offsets("segmented_sort", keys, offsets)
     n = keys.numel()
     nseg = offsets.numel() - 1
-    k_in = _aligned_copy(keys, torch)
+    k_in = _aligned_copy(keys)
     k_out = k_in.clone()
     p_in = p_out = None
     if payload is not None:
         if payload.shape != keys.shape or payload.device != keys.device or payload.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
             raise ValueError("segmented_sort: payload must be an int32 / uint32 tensor shaped like keys, on the same device")
-        p_in = _aligned_copy(payload, torch)
+        p_in = _aligned_copy(payload)
         p_out = p_in.clone()
     if n == 0 or nseg <= 0:
         return k_out, p_out
-    off = offsets if offsets.is_contiguous() and offsets.data_ptr() % 8 == 0 else offsets.clone(memory_format=torch.contiguous_format)
-    device = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
-    stream = torch.cuda.current_stream(keys.device).cuda_stream
-    eng = _segmented_engine(device, stream, name, p_in is not None, bool(descending), n)
-    eng.segmented_sort(k_in.data_ptr(), n, off.data_ptr(), nseg, k_out.data_ptr(),
-                       p_in.data_ptr() if p_in is not None else None, p_out.data_ptr() if p_out is not None else None)
+    off = _args.as_offsets(offsets)
+    eng = _segmented_engine(*_args.device_and_stream(keys), name, p_in is not None, bool(descending), n)
+    eng.segmented_sort(k_in.data_ptr(), n, off.data_ptr(), nseg, k_out.data_ptr(), _args.ptr(p_in), _args.ptr(p_out))
     eng.check_status()      # reports bad offsets of calls that have already finished
     return k_out, p_out
 
@@ -813,13 +816,12 @@ def sort_rows(x, descending: bool = False):
     rows, cols = x.shape
     if rows == 0 or cols == 0:
         return x.clone(), torch.zeros(x.shape, dtype=torch.int64, device=x.device)
-    if rows * cols > (1 << 31):
-        raise ValueError("sort_rows: at most 2^31 elements (rsx_segmented_sort's bound)")
+    _args.check_count("sort_rows", "rsx_segmented_sort", "elements", rows * cols)
     flat = x.contiguous().reshape(-1)
     offsets = torch.arange(0, rows + 1, device=x.device, dtype=torch.int64) * cols
     col = torch.arange(cols, device=x.device, dtype=torch.int64).to(torch.int32).repeat(rows)      # uint32 bits (cols may reach 2^31)
     values, idx = segmented_sort(flat, offsets, col, descending=descending)
-    return values.reshape(rows, cols), (idx.to(torch.int64) & 0xFFFFFFFF).reshape(rows, cols)      # the uint32 payload, unsigned
+    return values.reshape(rows, cols), _args.widen(idx).reshape(rows, cols)      # the uint32 payload, unsigned
 
 
 # -- top-k on torch tensors ---------------------------------------------------------------------------------------------------------
@@ -834,13 +836,7 @@ def segmented_topk(keys, offsets, k: int, largest: bool = True):
     negative-sign NaNs below -inf).  Bad offsets raise at the engine's next synchronisation (this call does not read them); their rows
     hold 0 / -1."""
     import torch
-    if keys.dim() != 1 or not keys.is_cuda:
-        raise ValueError("segmented_topk: keys must be a 1-D device tensor")
-    name = str(keys.dtype).replace("torch.", "")
-    if name not in _KEY_DTYPES:
-        raise TypeError(f"segmented_topk: unsupported key type {keys.dtype}")
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.device != keys.device:
-        raise ValueError("segmented_topk: offsets must be a 1-D int64 tensor on the keys' device")
+    name = _keys_and_offsets("segmented_topk", keys, offsets)
     k = int(k)
     if k < 0 or k > TOPK_MAX_K:
         raise ValueError(f"segmented_topk: k must be in [0, {TOPK_MAX_K}] (sort_rows / segmented_sort and a slice for larger k)")
@@ -850,11 +846,9 @@ def segmented_topk(keys, offsets, k: int, largest: bool = True):
     idx = torch.full((nseg, k), -1, dtype=torch.int32, device=keys.device)     # the uint32 output's bits: -1 marks an unwritten slot
     if n == 0 or nseg == 0 or k == 0:
         return values, idx.to(torch.int64)
-    k_in = _aligned_copy(keys, torch)
-    off = offsets if offsets.is_contiguous() and offsets.data_ptr() % 8 == 0 else offsets.clone(memory_format=torch.contiguous_format)
-    device = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
-    stream = torch.cuda.current_stream(keys.device).cuda_stream
-    eng = _segmented_engine(device, stream, name, False, bool(largest), n)      # largest: a descending engine
+    k_in = _aligned_copy(keys)
+    off = _args.as_offsets(offsets)
+    eng = _segmented_engine(*_args.device_and_stream(keys), name, False, bool(largest), n)      # largest: a descending engine
     eng.segmented_topk(k_in.data_ptr(), n, off.data_ptr(), nseg, k, values.data_ptr(), idx.data_ptr())
     eng.check_status()      # reports bad offsets of calls that have already finished
     return values, idx.to(torch.int64)      # uint32 positions below 2^31 (n <= 2^31): non-negative as int32
@@ -869,8 +863,7 @@ def topk(x, k: int, dim: int = -1, largest: bool = True, sorted: bool = True):
     import torch
     if not x.is_cuda:
         raise ValueError("topk: x must be a device tensor")
-    name = str(x.dtype).replace("torch.", "")
-    if name not in _KEY_DTYPES:
+    if _args.dtype_name(x) not in _KEY_DTYPES:
         raise TypeError(f"topk: unsupported dtype {x.dtype}")
     del sorted                                                  # the output is always sorted
     squeeze = x.dim() == 0          # torch.topk of a 0-d tensor: one row of one element, 0-d results
@@ -893,8 +886,7 @@ def topk(x, k: int, dim: int = -1, largest: bool = True, sorted: bool = True):
             sv, si = sort_rows(flat, descending=largest)
             v, i = sv[:, :k].contiguous(), si[:, :k].contiguous()
         else:
-            if rows * size > (1 << 31):
-                raise ValueError("topk: at most 2^31 elements (rsx_segmented_topk's bound)")
+            _args.check_count("topk", "rsx_segmented_topk", "elements", rows * size)
             offsets = torch.arange(0, rows + 1, device=x.device, dtype=torch.int64) * size
             v, i = segmented_topk(flat.reshape(-1), offsets, k, largest=largest)
         v, i = v.reshape(out_shape), i.reshape(out_shape)
@@ -919,13 +911,7 @@ def segmented_select(keys, offsets, ranks, descending: bool = False):
     above +inf; -0.0 below +0.0, negative-sign NaNs below -inf).  Bad offsets raise at the engine's next synchronisation (this call does
     not read them); their rows hold 0 / -1."""
     import torch
-    if keys.dim() != 1 or not keys.is_cuda:
-        raise ValueError("segmented_select: keys must be a 1-D device tensor")
-    name = str(keys.dtype).replace("torch.", "")
-    if name not in _KEY_DTYPES:
-        raise TypeError(f"segmented_select: unsupported key type {keys.dtype}")
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.device != keys.device:
-        raise ValueError("segmented_select: offsets must be a 1-D int64 tensor on the keys' device")
+    name = _keys_and_offsets("segmented_select", keys, offsets)
     nseg = max(offsets.numel() - 1, 0)
     if ranks.device != keys.device or ranks.is_floating_point() or ranks.dtype == torch.bool or ranks.dim() not in (1, 2) or ranks.shape[0] != nseg:
         raise ValueError("segmented_select: ranks must be an integer tensor [num_segments, R] or [num_segments] on the keys' device")
@@ -938,11 +924,9 @@ def segmented_select(keys, offsets, ranks, descending: bool = False):
         return values, idx.to(torch.int64)
     # uint32 bits for the engine; n <= 2^31, so everything outside [0, 2^31) selects nothing anyway: 0xFFFFFFFF
     r32 = torch.where((r64 < 0) | (r64 >= (1 << 31)), torch.full_like(r64, -1), r64).to(torch.int32)
-    k_in = _aligned_copy(keys, torch)
-    off = offsets if offsets.is_contiguous() and offsets.data_ptr() % 8 == 0 else offsets.clone(memory_format=torch.contiguous_format)
-    device = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
-    stream = torch.cuda.current_stream(keys.device).cuda_stream
-    eng = _segmented_engine(device, stream, name, False, bool(descending), n)
+    k_in = _aligned_copy(keys)
+    off = _args.as_offsets(offsets)
+    eng = _segmented_engine(*_args.device_and_stream(keys), name, False, bool(descending), n)
     if R <= SELECT_MAX_RANKS:
         r_in = r32.contiguous()
         eng.segmented_select(k_in.data_ptr(), n, off.data_ptr(), nseg, r_in.data_ptr(), R, values.data_ptr(), idx.data_ptr())
@@ -1000,8 +984,7 @@ def _select_along(what: str, x, dim: int, ranks):
     import torch
     if not x.is_cuda:
         raise ValueError(f"{what}: x must be a device tensor")
-    name = str(x.dtype).replace("torch.", "")
-    if name not in _KEY_DTYPES:
+    if _args.dtype_name(x) not in _KEY_DTYPES:
         raise TypeError(f"{what}: unsupported dtype {x.dtype}")
     if x.dim() == 0:
         x = x.reshape(1)
@@ -1016,8 +999,7 @@ def _select_along(what: str, x, dim: int, ranks):
     out_shape = xm.shape[:-1] + (ranks.numel(),)
     if rows == 0:
         return torch.empty(out_shape, dtype=x.dtype, device=x.device), torch.empty(out_shape, dtype=torch.int64, device=x.device), dim
-    if rows * size > (1 << 31):
-        raise ValueError(f"{what}: at most 2^31 elements (rsx_segmented_select's bound)")
+    _args.check_count(what, "rsx_segmented_select", "elements", rows * size)
     flat = xm.contiguous().reshape(-1)
     offsets = torch.arange(0, rows + 1, device=x.device, dtype=torch.int64) * size
     v, i = segmented_select(flat, offsets, ranks.reshape(1, -1).expand(rows, -1), descending=False)
@@ -1107,12 +1089,9 @@ def _unique_call(what: str, keys, offsets, want_inverse: bool, want_counts: bool
     import torch
     if not keys.is_cuda:
         raise ValueError(f"{what}: the input must be a device tensor (there is no CPU path)")
-    name = str(keys.dtype).replace("torch.", "")
-    if name not in _KEY_DTYPES:
-        raise TypeError(f"{what}: unsupported key type {keys.dtype}")
+    name = _args.key_name(what, keys)
     n = keys.numel()
-    if n > (1 << 31):
-        raise ValueError(f"{what}: at most 2^31 elements (rsx_segmented_unique's bound)")
+    _args.check_count(what, "rsx_segmented_unique", "elements", n)
     nseg = 1 if offsets is None else max(offsets.numel() - 1, 0)
     dev = keys.device
     run_offsets = torch.zeros(nseg + 1, dtype=torch.int64, device=dev)
@@ -1123,20 +1102,15 @@ def _unique_call(what: str, keys, offsets, want_inverse: bool, want_counts: bool
     first = torch.empty(n, dtype=torch.int32, device=dev) if want_first else None
     total = 0
     if n > 0 and nseg > 0:
-        k_in = _aligned_copy(keys, torch)
-        off = None
-        if offsets is not None:
-            off = offsets if offsets.is_contiguous() and offsets.data_ptr() % 8 == 0 else offsets.clone(memory_format=torch.contiguous_format)
-        device = dev.index if dev.index is not None else torch.cuda.current_device()
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        k_in = _aligned_copy(keys)
+        off = _args.as_offsets(offsets)
         positions = (want_inverse or want_first) and not consecutive         # only these travel through the sort as its payload
-        eng = _segmented_engine(device, stream, name, positions, bool(descending), n)
-        eng.segmented_unique(k_in.data_ptr(), n, off.data_ptr() if off is not None else None, nseg, values.data_ptr(), run_offsets.data_ptr(),
-                             counts.data_ptr() if want_counts else None, first.data_ptr() if want_first else None,
-                             inverse.data_ptr() if want_inverse else None, consecutive=consecutive)
+        eng = _segmented_engine(*_args.device_and_stream(keys), name, positions, bool(descending), n)
+        eng.segmented_unique(k_in.data_ptr(), n, _args.ptr(off), nseg, values.data_ptr(), run_offsets.data_ptr(),
+                             _args.ptr(counts), _args.ptr(first), _args.ptr(inverse), consecutive=consecutive)
         total = int(run_offsets[-1].item())         # the one read-back (a host synchronisation): how many runs there are
         eng.check_status()      # reports bad offsets (the call has finished)
-    widen = lambda t: None if t is None else (t.to(torch.int64) & 0xFFFFFFFF)
+    widen = _args.widen
     return values[:total], run_offsets, widen(inverse), widen(None if counts is None else counts[:total]), widen(None if first is None else first[:total])
 
 
@@ -1151,13 +1125,11 @@ def segmented_unique(keys, offsets, return_inverse: bool = False, return_counts:
     follow IEEE 754 totalOrder, so -0.0 and +0.0 are two values and NaNs with equal bits are one (torch.unique merges the zeros and keeps
     every NaN apart).  values and the per-run outputs are trimmed to run_offsets[-1], which reads one int64 back: one host synchronisation
     per call, as torch.unique has.  Bad offsets raise RadixSortError."""
-    import torch
     if keys.dim() != 1:
         raise ValueError("segmented_unique: keys must be a 1-D device tensor")
     if not keys.is_cuda:
         raise ValueError("segmented_unique: keys must be a 1-D device tensor (there is no CPU path)")
-    if offsets is None or offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.device != keys.device:
-        raise ValueError("segmented_unique: offsets must be a 1-D int64 tensor on the keys' device")
+    _args.check_offsets("segmented_unique", offsets, keys.device)
     v, ro, inv, cnt, fst = _unique_call("segmented_unique", keys, offsets, return_inverse, return_counts, return_first, descending, consecutive)
     return (v, ro) + ((inv,) if return_inverse else ()) + ((cnt,) if return_counts else ()) + ((fst,) if return_first else ())
 
@@ -1190,7 +1162,7 @@ def unique_consecutive(x, return_inverse: bool = False, return_counts: bool = Fa
 
 # -- reduce by key on torch tensors -----------------------------------------------------------------------------------------------------
 _REDUCE_OPS = {"sum": REDUCE_SUM, "min": REDUCE_MIN, "max": REDUCE_MAX, "mean": REDUCE_SUM}
-_VALUE_KINDS = {"int32": VALUE_INT32, "int64": VALUE_INT64, "float32": VALUE_FLOAT32, "float64": VALUE_FLOAT64}
+_VALUE_KINDS = _args.VALUE_KINDS    # dtype name -> value kind
 
 
 def _reduce_call(what: str, keys, values, offsets, op: str, descending: bool, consecutive: bool):
@@ -1199,12 +1171,8 @@ def _reduce_call(what: str, keys, values, offsets, op: str, descending: bool, co
     import torch
     if op not in _REDUCE_OPS:
         raise ValueError(f"{what}: op must be one of 'sum', 'min', 'max', 'mean', not {op!r}")
-    name = str(keys.dtype).replace("torch.", "")
-    if name not in _KEY_DTYPES:
-        raise TypeError(f"{what}: unsupported key type {keys.dtype}")
-    vname = str(values.dtype).replace("torch.", "")
-    if vname not in _VALUE_KINDS:
-        raise TypeError(f"{what}: unsupported value type {values.dtype} (int32, int64, float32 or float64)")
+    name = _args.key_name(what, keys)
+    vkind = _args.value_kind(what, values)
     if op == "mean" and not values.dtype.is_floating_point:
         raise TypeError(f"{what}: the mean of integer values is not defined here (convert them to a float type)")
     if not keys.is_cuda or not values.is_cuda:
@@ -1212,8 +1180,7 @@ def _reduce_call(what: str, keys, values, offsets, op: str, descending: bool, co
     if values.shape != keys.shape or values.device != keys.device:
         raise ValueError(f"{what}: values must be shaped like keys and live on the same device")
     n = keys.numel()
-    if n > (1 << 31):
-        raise ValueError(f"{what}: at most 2^31 elements (rsx_segmented_reduce_by_key's bound)")
+    _args.check_count(what, "rsx_segmented_reduce_by_key", "elements", n)
     nseg = 1 if offsets is None else max(offsets.numel() - 1, 0)
     dev = keys.device
     run_offsets = torch.zeros(nseg + 1, dtype=torch.int64, device=dev)
@@ -1222,20 +1189,15 @@ def _reduce_call(what: str, keys, values, offsets, op: str, descending: bool, co
     counts = torch.empty(n, dtype=torch.int32, device=dev)
     total = 0
     if n > 0 and nseg > 0:
-        k_in = _aligned_copy(keys, torch)
+        k_in = _aligned_copy(keys)
         v_in = values.contiguous()
-        off = None
-        if offsets is not None:
-            off = offsets if offsets.is_contiguous() and offsets.data_ptr() % 8 == 0 else offsets.clone(memory_format=torch.contiguous_format)
-        device = dev.index if dev.index is not None else torch.cuda.current_device()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        eng = _segmented_engine(device, stream, name, not consecutive, bool(descending), n)      # the positions travel as the sort's payload
-        eng.segmented_reduce_by_key(k_in.data_ptr(), v_in.data_ptr(), n, off.data_ptr() if off is not None else None, nseg, _REDUCE_OPS[op],
-                                    _VALUE_KINDS[vname], ukeys.data_ptr(), run_offsets.data_ptr(), reduced.data_ptr(), counts.data_ptr(),
-                                    consecutive=consecutive)
+        off = _args.as_offsets(offsets)
+        eng = _segmented_engine(*_args.device_and_stream(keys), name, not consecutive, bool(descending), n)      # the positions travel as the sort's payload
+        eng.segmented_reduce_by_key(k_in.data_ptr(), v_in.data_ptr(), n, _args.ptr(off), nseg, _REDUCE_OPS[op], vkind, ukeys.data_ptr(),
+                                    run_offsets.data_ptr(), reduced.data_ptr(), counts.data_ptr(), consecutive=consecutive)
         total = int(run_offsets[-1].item())         # the one read-back (a host synchronisation): how many runs there are
         eng.check_status()      # reports bad offsets (the call has finished)
-    cnt = counts[:total].to(torch.int64) & 0xFFFFFFFF
+    cnt = _args.widen(counts[:total])
     red = reduced[:total]
     if op == "mean":
         red = red / cnt.to(red.dtype)
@@ -1250,11 +1212,9 @@ def segmented_reduce_by_key(keys, values, offsets, op: str = "sum", descending: 
     values only) is the sum divided by the count.  Float sums are added in an order fixed by the input alone: the same call gives the same
     bits every time, which index_add_ does not.  consecutive=True sorts nothing and reduces the runs of adjacent equal keys.  Reads the
     number of runs back: one host synchronisation per call.  Bad offsets raise RadixSortError."""
-    import torch
     if keys.dim() != 1 or values.dim() != 1:
         raise ValueError("segmented_reduce_by_key: keys and values must be 1-D device tensors")
-    if offsets is None or offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.device != keys.device:
-        raise ValueError("segmented_reduce_by_key: offsets must be a 1-D int64 tensor on the keys' device")
+    _args.check_offsets("segmented_reduce_by_key", offsets, keys.device)
     k, ro, red, cnt = _reduce_call("segmented_reduce_by_key", keys, values, offsets, op, descending, consecutive)
     return (k, ro, red) + ((cnt,) if return_counts else ())
 
@@ -1280,40 +1240,24 @@ _SCAN_ENGINE_CAPACITY = 1 << 12
 
 
 def _scan_engine(device: int, stream: int, key_bytes: int) -> "Engine":
-    key = (device, stream, key_bytes)
-    eng = _SCAN_ENGINES.get(key)
-    if eng is None:
-        eng = Engine("uint32" if key_bytes == 4 else "uint64", _SCAN_ENGINE_CAPACITY, payload=False, device=device)
-        eng.set_stream(stream)
-        _SCAN_ENGINES[key] = eng
-    return eng
+    return _cached_engine(_SCAN_ENGINES, (device, stream, key_bytes), "uint32" if key_bytes == 4 else "uint64", _SCAN_ENGINE_CAPACITY)
 
 
 def _scan_call(what: str, keys, values, offsets, op: str, exclusive: bool, out):
     """One rsx_segmented_scan call on 1-D device tensors (keys None: segments only; offsets None: one segment)."""
-    import torch
     if op not in _SCAN_OPS:
         raise ValueError(f"{what}: op must be one of 'sum', 'min', 'max', not {op!r}")
-    vname = str(values.dtype).replace("torch.", "")
-    if vname not in _VALUE_KINDS:
-        raise TypeError(f"{what}: unsupported value type {values.dtype} (int32, int64, float32 or float64)")
-    key_bytes = 4
-    if keys is not None:
-        name = str(keys.dtype).replace("torch.", "")
-        if name not in _KEY_DTYPES:
-            raise TypeError(f"{what}: unsupported key type {keys.dtype}")
-        key_bytes = _KEY_DTYPES[name][0]
+    vkind = _args.value_kind(what, values)
+    key_bytes = 4 if keys is None else _KEY_DTYPES[_args.key_name(what, keys)][0]
     if not values.is_cuda or (keys is not None and not keys.is_cuda):
         raise ValueError(f"{what}: keys and values must be device tensors (there is no CPU path)")
     if values.dim() != 1 or (keys is not None and (keys.shape != values.shape or keys.device != values.device)):
         raise ValueError(f"{what}: values must be 1-D, and keys shaped like them on the same device")
-    if offsets is not None and (offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.device != values.device):
-        raise ValueError(f"{what}: offsets must be a 1-D int64 tensor on the values' device")
+    _args.check_offsets(what, offsets, values.device, none_ok=True, whose="values'")
     if out is not None and (out.dtype != values.dtype or out.shape != values.shape or out.device != values.device or not out.is_contiguous()):
         raise ValueError(f"{what}: out must be a contiguous tensor like values (out=values scans in place)")
     n = values.numel()
-    if n > (1 << 31):
-        raise ValueError(f"{what}: at most 2^31 elements (rsx_segmented_scan's bound)")
+    _args.check_count(what, "rsx_segmented_scan", "elements", n)
     in_place = out is not None and out.data_ptr() == values.data_ptr() and values.is_contiguous()
     v_in = values if values.is_contiguous() else values.contiguous()          # (aligned to its element size either way)
     if out is None:
@@ -1323,15 +1267,11 @@ def _scan_call(what: str, keys, values, offsets, op: str, exclusive: bool, out):
     nseg = 1 if offsets is None else max(offsets.numel() - 1, 0)
     if n == 0 or nseg == 0:
         return out
-    k_in = None if keys is None else _aligned_copy(keys, torch)
-    off = None
-    if offsets is not None:
-        off = offsets if offsets.is_contiguous() and offsets.data_ptr() % 8 == 0 else offsets.clone(memory_format=torch.contiguous_format)
-    dev = values.device
-    device = dev.index if dev.index is not None else torch.cuda.current_device()
-    eng = _scan_engine(device, torch.cuda.current_stream(dev).cuda_stream, key_bytes)
-    eng.segmented_scan(None if k_in is None else k_in.data_ptr(), out.data_ptr() if in_place else v_in.data_ptr(), n,
-                       None if off is None else off.data_ptr(), nseg, _SCAN_OPS[op], _VALUE_KINDS[vname], out.data_ptr(), exclusive=bool(exclusive))
+    k_in = None if keys is None else _aligned_copy(keys)
+    off = _args.as_offsets(offsets)
+    eng = _scan_engine(*_args.device_and_stream(values), key_bytes)
+    eng.segmented_scan(_args.ptr(k_in), out.data_ptr() if in_place else v_in.data_ptr(), n, _args.ptr(off), nseg, _SCAN_OPS[op], vkind,
+                       out.data_ptr(), exclusive=bool(exclusive))
     eng.check_status()      # reports bad offsets of calls that have already finished; no synchronisation
     return out
 
@@ -1362,7 +1302,7 @@ def cumsum(x, dim: int = -1):
     x's dtype: an integer dtype narrower than int64 (int32 here) is NOT promoted to int64 as torch does, its sums wrap.  Float sums are
     bitwise reproducible (segmented_scan).  Supported dtypes: int32, int64, float32, float64 (TypeError otherwise)."""
     import torch
-    if str(x.dtype).replace("torch.", "") not in _VALUE_KINDS:
+    if _args.dtype_name(x) not in _VALUE_KINDS:
         raise TypeError(f"cumsum: unsupported dtype {x.dtype} (int32, int64, float32 or float64)")
     if not x.is_cuda:
         raise ValueError("cumsum: x must be a device tensor")
@@ -1386,27 +1326,25 @@ def cumsum(x, dim: int = -1):
 _SEGREDUCE_OPS = {"sum": REDUCE_SUM, "min": REDUCE_MIN, "max": REDUCE_MAX, "mean": REDUCE_SUM, "argmin": REDUCE_ARGMIN, "argmax": REDUCE_ARGMAX}
 
 
-def _segreduce_check(what: str, values, op: str) -> str:
+def _segreduce_check(what: str, values, op: str) -> int:
+    """the op, then the value type (its kind), then the device"""
     if op not in _SEGREDUCE_OPS:
         raise ValueError(f"{what}: op must be one of 'sum', 'min', 'max', 'mean', 'argmin', 'argmax', not {op!r}")
-    vname = str(values.dtype).replace("torch.", "")
-    if vname not in _VALUE_KINDS:
-        raise TypeError(f"{what}: unsupported value type {values.dtype} (int32, int64, float32 or float64)")
-    if op == "mean" and not vname.startswith("float"):
+    vkind = _args.value_kind(what, values)
+    if op == "mean" and not values.dtype.is_floating_point:
         raise TypeError(f"{what}: 'mean' needs float32 or float64 values, not {values.dtype}")
     if not values.is_cuda:
         raise ValueError(f"{what}: values must be a device tensor (there is no CPU path)")
-    return vname
+    return vkind
 
 
 def _segreduce_call(what: str, values, offsets, nseg: int, op: str, want_values: bool, want_index: bool):
     """One rsx_segmented_reduce call on a 1-D contiguous device tensor; offsets None: one segment.  Returns (values or None, the uint32
     indices viewed as int32, i.e. -1 for an empty segment, or None)."""
     import torch
-    vname = _segreduce_check(what, values, op)
+    vkind = _segreduce_check(what, values, op)
     n = values.numel()
-    if n > (1 << 31):
-        raise ValueError(f"{what}: at most 2^31 elements (rsx_segmented_reduce's bound)")
+    _args.check_count(what, "rsx_segmented_reduce", "elements", n)
     dev = values.device
     code = _SEGREDUCE_OPS[op]
     if want_index and code == REDUCE_MIN:
@@ -1418,13 +1356,9 @@ def _segreduce_call(what: str, values, offsets, nseg: int, op: str, want_values:
     iout = torch.empty(nseg, dtype=torch.int32, device=dev) if arg else None
     if nseg == 0:
         return vout, iout
-    off = None
-    if offsets is not None:
-        off = offsets if offsets.is_contiguous() and offsets.data_ptr() % 8 == 0 else offsets.clone(memory_format=torch.contiguous_format)
-    device = dev.index if dev.index is not None else torch.cuda.current_device()
-    eng = _scan_engine(device, torch.cuda.current_stream(dev).cuda_stream, 4)
-    eng.segmented_reduce(values.data_ptr() if n else None, n, None if off is None else off.data_ptr(), nseg, code, _VALUE_KINDS[vname],
-                         None if vout is None else vout.data_ptr(), None if iout is None else iout.data_ptr())
+    off = _args.as_offsets(offsets)
+    eng = _scan_engine(*_args.device_and_stream(values), 4)
+    eng.segmented_reduce(_args.ptr_nonempty(values), n, _args.ptr(off), nseg, code, vkind, _args.ptr(vout), _args.ptr(iout))
     eng.check_status()      # reports bad offsets of calls that have already finished; no synchronisation
     return vout, iout
 
@@ -1444,8 +1378,7 @@ def segmented_reduce(values, offsets, op: str = "sum", return_index: bool = Fals
         raise ValueError("segmented_reduce: return_index goes with op 'min' or 'max'")
     if values.dim() != 1:
         raise ValueError("segmented_reduce: values must be 1-D")
-    if offsets is None or offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.device != values.device:
-        raise ValueError("segmented_reduce: offsets must be a 1-D int64 tensor on the values' device")
+    _args.check_offsets("segmented_reduce", offsets, values.device, whose="values'")
     nseg = max(offsets.numel() - 1, 0)
     v_in = values if values.is_contiguous() else values.contiguous()
     arg = op in ("argmin", "argmax")
@@ -1522,7 +1455,7 @@ def _expand_offsets(what: str, offsets, torch):
         raise ValueError(f"{what}: offsets must be a device tensor (there is no CPU path)")
     if offsets.dtype != torch.int64 or offsets.dim() != 1:
         raise ValueError(f"{what}: offsets must be a 1-D int64 device tensor")
-    return offsets if offsets.is_contiguous() else offsets.contiguous()
+    return _args.as_offsets(offsets)
 
 
 def _expand_total(what: str, off, n):
@@ -1549,12 +1482,10 @@ def _expand_call(what: str, off, n: int, values=None, starts=None, want_segment:
     if want_rank:
         rout = torch.zeros(n, dtype=torch.int32, device=dev)
     if n and nseg:
-        device = dev.index if dev.index is not None else torch.cuda.current_device()
-        eng = _scan_engine(device, torch.cuda.current_stream(dev).cuda_stream, 4)
-        eng.segmented_expand(None if values is None else values.data_ptr(), 0 if values is None else values.numel(),
-                             4 if values is None else values.element_size(), off.data_ptr(), nseg, n,
-                             None if starts is None else starts.data_ptr(), None if vout is None else vout.data_ptr(),
-                             None if sout is None else sout.data_ptr(), None if rout is None else rout.data_ptr())
+        ptr = _args.ptr
+        eng = _scan_engine(*_args.device_and_stream(off), 4)
+        eng.segmented_expand(ptr(values), 0 if values is None else values.numel(), 4 if values is None else values.element_size(),
+                             off.data_ptr(), nseg, n, ptr(starts), ptr(vout), ptr(sout), ptr(rout))
         eng.check_status()      # reports bad input of calls that have already finished; no synchronisation
     return vout, sout, rout
 
@@ -1731,13 +1662,7 @@ _SEARCH_ENGINES: dict = {}
 
 
 def _search_engine(device: int, stream: int, dtype_name: str, descending: bool) -> "Engine":
-    key = (device, stream, dtype_name, descending)
-    eng = _SEARCH_ENGINES.get(key)
-    if eng is None:
-        eng = Engine(dtype_name, _SCAN_ENGINE_CAPACITY, payload=False, device=device, descending=descending)
-        eng.set_stream(stream)
-        _SEARCH_ENGINES[key] = eng
-    return eng
+    return _cached_engine(_SEARCH_ENGINES, (device, stream, dtype_name, descending), dtype_name, _SCAN_ENGINE_CAPACITY, descending=descending)
 
 
 def _search_call(what: str, hay, offsets, values, value_offsets, right: bool, descending: bool):
@@ -1747,39 +1672,30 @@ def _search_call(what: str, hay, offsets, values, value_offsets, right: bool, de
     for name, t in (("the sorted keys", hay), ("values", values)):
         if not torch.is_tensor(t):
             raise TypeError(f"{what}: {name} must be a tensor")
-    name = str(hay.dtype).replace("torch.", "")
-    if name not in _KEY_DTYPES:
-        raise TypeError(f"{what}: unsupported key type {hay.dtype}")
+    name = _args.key_name(what, hay)
     if values.dtype != hay.dtype:
         raise TypeError(f"{what}: values are {values.dtype}, the sorted keys {hay.dtype} (convert one of them: the search compares keys of one type)")
     if not hay.is_cuda or not values.is_cuda:
         raise ValueError(f"{what}: the sorted keys and the values must be device tensors (there is no CPU path)")
     if hay.dim() != 1 or values.dim() != 1 or values.device != hay.device:
         raise ValueError(f"{what}: the sorted keys and the values must be 1-D tensors on one device")
-    for oname, o in (("offsets", offsets), ("value_offsets", value_offsets)):
-        if o is not None and (o.dtype != torch.int64 or o.dim() != 1 or o.device != hay.device):
-            raise ValueError(f"{what}: {oname} must be a 1-D int64 tensor on the keys' device")
+    _args.check_offsets(what, offsets, hay.device, none_ok=True)
+    _args.check_offsets(what, value_offsets, hay.device, "value_offsets", none_ok=True)
     if value_offsets is not None and (offsets is None or value_offsets.numel() != offsets.numel()):
         raise ValueError(f"{what}: value_offsets needs offsets with the same number of entries")
     n, nq = hay.numel(), values.numel()
-    if n > (1 << 31) or nq > (1 << 31):
-        raise ValueError(f"{what}: at most 2^31 keys and 2^31 values (rsx_segmented_search's bound)")
+    _args.check_count(what, "rsx_segmented_search", "keys and 2^31 values", n, nq)
     nseg = 1 if offsets is None else max(offsets.numel() - 1, 0)
     if offsets is not None and value_offsets is None and nseg > 0 and nq % nseg != 0:
         raise ValueError(f"{what}: without value_offsets every segment has the same number of values, and {nq} is no multiple of {nseg} segments")
     out = torch.zeros(nq, dtype=torch.int32, device=hay.device)
     if nq == 0 or nseg == 0:
         return out
-    k_in = _aligned_copy(hay, torch)
+    k_in = _aligned_copy(hay)
     q_in = values if values.is_contiguous() else values.contiguous()          # (aligned to its element size either way)
-    offs = []
-    for o in (offsets, value_offsets):
-        offs.append(None if o is None else o if o.is_contiguous() and o.data_ptr() % 8 == 0 else o.clone(memory_format=torch.contiguous_format))
-    dev = hay.device
-    device = dev.index if dev.index is not None else torch.cuda.current_device()
-    eng = _search_engine(device, torch.cuda.current_stream(dev).cuda_stream, name, bool(descending))
-    eng.segmented_search(k_in.data_ptr() if n else None, n, None if offs[0] is None else offs[0].data_ptr(), nseg, q_in.data_ptr(), nq,
-                         None if offs[1] is None else offs[1].data_ptr(), out.data_ptr(), right=bool(right))
+    off, qoff = _args.as_offsets(offsets), _args.as_offsets(value_offsets)
+    eng = _search_engine(*_args.device_and_stream(hay), name, bool(descending))
+    eng.segmented_search(_args.ptr_nonempty(k_in), n, _args.ptr(off), nseg, q_in.data_ptr(), nq, _args.ptr(qoff), out.data_ptr(), right=bool(right))
     eng.check_status()      # reports bad offsets of calls that have already finished; no synchronisation
     return out
 
@@ -1857,9 +1773,7 @@ def _compact_keys_check(what: str, keys) -> str:
     import torch
     if not torch.is_tensor(keys):
         raise TypeError(f"{what}: the input must be a tensor")
-    name = str(keys.dtype).replace("torch.", "")
-    if name not in _KEY_DTYPES:
-        raise TypeError(f"{what}: unsupported key type {keys.dtype}")
+    name = _args.key_name(what, keys)
     if not keys.is_cuda:
         raise ValueError(f"{what}: the input must be a device tensor (there is no CPU path)")
     return name
@@ -1881,8 +1795,7 @@ def _compact_call(what: str, keys, offsets, mask, bounds, strict: bool, invert: 
         if mask.device != keys.device or mask.shape != keys.shape:
             raise ValueError(f"{what}: the mask must be on the keys' device and of the keys' shape")
     n = keys.numel()
-    if n > (1 << 31):
-        raise ValueError(f"{what}: at most 2^31 elements (rsx_segmented_compact's bound)")
+    _args.check_count(what, "rsx_segmented_compact", "elements", n)
     nseg = 1 if offsets is None else max(offsets.numel() - 1, 0)
     if bounds is not None:
         if not torch.is_tensor(bounds) or bounds.dtype != keys.dtype:
@@ -1896,24 +1809,20 @@ def _compact_call(what: str, keys, offsets, mask, bounds, strict: bool, invert: 
     index = (torch.zeros if partition else torch.empty)(n, dtype=torch.int32, device=dev) if want_index else None
     total = n
     if n > 0 and nseg > 0:
-        k_in = _aligned_copy(keys, torch)
-        off = None
-        if offsets is not None:
-            off = offsets if offsets.is_contiguous() and offsets.data_ptr() % 8 == 0 else offsets.clone(memory_format=torch.contiguous_format)
+        ptr = _args.ptr
+        k_in = _aligned_copy(keys)
+        off = _args.as_offsets(offsets)
         m_in = None if mask is None else mask if mask.is_contiguous() else mask.contiguous()
         b_in = None if bounds is None else bounds.contiguous().reshape(-1)
-        device = dev.index if dev.index is not None else torch.cuda.current_device()
-        eng = _search_engine(device, torch.cuda.current_stream(dev).cuda_stream, name, bool(descending))
-        eng.segmented_compact(k_in.data_ptr(), n, off.data_ptr() if off is not None else None, nseg, m_in.data_ptr() if m_in is not None else None,
-                              b_in.data_ptr() if b_in is not None else None, values.data_ptr() if want_keys else None,
-                              index.data_ptr() if want_index else None, kept.data_ptr(), partition=partition, invert=invert, strict=strict)
+        eng = _search_engine(*_args.device_and_stream(keys), name, bool(descending))
+        eng.segmented_compact(k_in.data_ptr(), n, ptr(off), nseg, ptr(m_in), ptr(b_in), ptr(values), ptr(index), kept.data_ptr(),
+                              partition=partition, invert=invert, strict=strict)
         if not partition:
             total = int(kept[-1].item())            # the one read-back (a host synchronisation): how many were kept
         eng.check_status()      # reports bad offsets of calls that have already finished
     elif not partition:
         total = 0
-    widen = lambda t: None if t is None else (t.to(torch.int64) & 0xFFFFFFFF)
-    return (None if values is None else values[:total]), kept, widen(None if index is None else index[:total])
+    return (None if values is None else values[:total]), kept, _args.widen(None if index is None else index[:total])
 
 
 def segmented_compact(keys, offsets, mask=None, bound=None, strict: bool = False, invert: bool = False, descending: bool = False,
@@ -1928,12 +1837,10 @@ def segmented_compact(keys, offsets, mask=None, bound=None, strict: bool = False
     drops nothing: values and index are shaped like keys, every segment holds its kept elements first and the others behind them, both in
     input order, kept_offsets[s+1] - kept_offsets[s] is the split of segment s, positions outside [offsets[0], offsets[-1]) hold the
     input's keys and index 0, and nothing is read back.  Bad offsets raise RadixSortError."""
-    import torch
     _compact_keys_check("segmented_compact", keys)
     if keys.dim() != 1:
         raise ValueError("segmented_compact: keys must be a 1-D device tensor")
-    if offsets is not None and (offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.device != keys.device):
-        raise ValueError("segmented_compact: offsets must be a 1-D int64 tensor on the keys' device (or None: one segment)")
+    _args.check_offsets("segmented_compact", offsets, keys.device, none_ok=True, hint=" (or None: one segment)")
     v, ko, idx = _compact_call("segmented_compact", keys, offsets, mask, bound, strict, invert, descending, partition, True, return_index)
     return (v, ko) + ((idx,) if return_index else ())
 
@@ -1961,22 +1868,19 @@ def nonzero(x, as_tuple: bool = False):
         raise TypeError("nonzero: x must be a tensor")
     if not x.is_cuda:
         raise ValueError("nonzero: x must be a device tensor (there is no CPU path)")
-    if x.numel() > (1 << 31):
-        raise ValueError("nonzero: at most 2^31 elements (rsx_segmented_compact's bound)")
+    _args.check_count("nonzero", "rsx_segmented_compact", "elements", x.numel())
     flat_mask = (x != 0).contiguous().reshape(-1)
     # positions only: in mask form without a key output the call does not read the keys, so the (16-byte aligned) mask stands in for them
-    flat_mask = _aligned_copy(flat_mask, torch)
+    flat_mask = _aligned_copy(flat_mask)
     idx = torch.empty(flat_mask.numel(), dtype=torch.int32, device=x.device)
     kept = torch.zeros(2, dtype=torch.int64, device=x.device)
     total = 0
     if flat_mask.numel() > 0:
-        dev = x.device
-        device = dev.index if dev.index is not None else torch.cuda.current_device()
-        eng = _search_engine(device, torch.cuda.current_stream(dev).cuda_stream, "uint32", False)
+        eng = _search_engine(*_args.device_and_stream(x), "uint32", False)
         eng.segmented_compact(flat_mask.data_ptr(), flat_mask.numel(), None, 1, flat_mask.data_ptr(), None, None, idx.data_ptr(), kept.data_ptr())
         total = int(kept[-1].item())                # the one read-back (a host synchronisation): how many there are
         eng.check_status()
-    idx = idx[:total].to(torch.int64) & 0xFFFFFFFF
+    idx = _args.widen(idx[:total])
     cols = []
     rem = idx
     for size in reversed(x.shape):
@@ -2047,21 +1951,17 @@ def _hist_call(what: str, keys, offsets, nseg: int, bins, lo, hi, width_shift: i
         elif lo is None or hi is None:
             raise ValueError(f"{what}: float keys need lo and hi in the even form")
     n = keys.numel()
-    if n > (1 << 31) or nseg * nb > _HIST_MAX_COUNTERS:
+    if n > _args.MAX_ELEMENTS or nseg * nb > _HIST_MAX_COUNTERS:
         raise ValueError(f"{what}: at most 2^31 elements and 2^31 counters (rsx_segmented_histogram's bounds)")
-    dev = keys.device
-    counts = torch.zeros((nseg, nb), dtype=torch.int32, device=dev)
+    counts = torch.zeros((nseg, nb), dtype=torch.int32, device=keys.device)
     if nseg > 0:
-        k_in = _aligned_copy(keys, torch)
-        off = None
-        if offsets is not None:
-            off = offsets if offsets.is_contiguous() and offsets.data_ptr() % 8 == 0 else offsets.clone(memory_format=torch.contiguous_format)
-        device = dev.index if dev.index is not None else torch.cuda.current_device()
-        eng = _search_engine(device, torch.cuda.current_stream(dev).cuda_stream, name, bool(descending))
-        eng.segmented_histogram(k_in.data_ptr() if n else None, n, off.data_ptr() if off is not None else None, nseg, nb, counts.data_ptr(),
-                                d_edges=edges.data_ptr() if edges is not None else None, lo=lo or 0, hi=hi or 0, width_shift=int(width_shift))
+        k_in = _aligned_copy(keys)
+        off = _args.as_offsets(offsets)
+        eng = _search_engine(*_args.device_and_stream(keys), name, bool(descending))
+        eng.segmented_histogram(_args.ptr_nonempty(k_in), n, _args.ptr(off), nseg, nb, counts.data_ptr(), d_edges=_args.ptr(edges), lo=lo or 0,
+                                hi=hi or 0, width_shift=int(width_shift))
         eng.check_status()      # reports bad offsets of calls that have already finished; no synchronisation
-    return counts.to(torch.int64) & 0xFFFFFFFF
+    return _args.widen(counts)
 
 
 def segmented_histogram(keys, offsets, bins, lo=None, hi=None, width_shift: int = 0, descending: bool = False):
@@ -2072,19 +1972,17 @@ def segmented_histogram(keys, offsets, bins, lo=None, hi=None, width_shift: int 
     float keys to bin min(B - 1, floor((x - lo) * (B / (hi - lo)))) for lo <= x <= hi; descending=True numbers those bins backwards.
     Keys that fall into no bin are dropped.  offsets None: one segment.  Never synchronises with the host; bad offsets (all counters are
     zero then) raise RadixSortError at a later call or synchronisation of the engine."""
-    import torch
     _compact_keys_check("segmented_histogram", keys)
     if keys.dim() != 1:
         raise ValueError("segmented_histogram: keys must be a 1-D device tensor")
-    if offsets is not None and (offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.device != keys.device):
-        raise ValueError("segmented_histogram: offsets must be a 1-D int64 tensor on the keys' device (or None: one segment)")
+    _args.check_offsets("segmented_histogram", offsets, keys.device, none_ok=True, hint=" (or None: one segment)")
     nseg = 1 if offsets is None else max(offsets.numel() - 1, 0)
     return _hist_call("segmented_histogram", keys, offsets, nseg, bins, lo, hi, width_shift, descending)
 
 
 def _hist_int_check(what: str, x) -> str:
     import torch
-    if torch.is_tensor(x) and str(x.dtype).replace("torch.", "") not in _INT_KEY_DTYPES:
+    if torch.is_tensor(x) and _args.dtype_name(x) not in _INT_KEY_DTYPES:
         raise TypeError(f"{what}: the input must be an integer tensor (int32, int64, uint32 or uint64), not {x.dtype}")
     return _compact_keys_check(what, x)
 
@@ -2105,10 +2003,8 @@ def bincount(x, minlength: int = 0, num_bins=None):
     elif x.numel() == 0:
         nb = int(minlength)
     else:
-        k_in = _aligned_copy(x, torch)
-        dev = x.device
-        device = dev.index if dev.index is not None else torch.cuda.current_device()
-        eng = _search_engine(device, torch.cuda.current_stream(dev).cuda_stream, name, False)
+        k_in = _aligned_copy(x)
+        eng = _search_engine(*_args.device_and_stream(x), name, False)
         lo, hi = eng.key_range(k_in.data_ptr(), k_in.numel())          # of key ^ sign bit for signed keys: the one read-back
         sign = (1 << (8 * _KEY_DTYPES[name][0] - 1)) if _KEY_DTYPES[name][1] == KEY_SIGNED else 0
         if lo < sign:
@@ -2219,49 +2115,21 @@ def _merge_call(what: str, a, a_offsets, b, b_offsets, payload_a, payload_b, des
     """One rsx_segmented_merge call on 1-D device tensors (both offsets None: one segment).  Returns (keys, out_offsets, payload, index):
     keys, payload and index have na + nb entries, zero (index: -1) from out_offsets[-1] on; nothing is read back."""
     import torch
-    for name, t in (("a", a), ("b", b)):
-        if not torch.is_tensor(t):
-            raise TypeError(f"{what}: {name} must be a tensor")
-    name = str(a.dtype).replace("torch.", "")
-    if name not in _KEY_DTYPES:
-        raise TypeError(f"{what}: unsupported key type {a.dtype}")
-    if b.dtype != a.dtype:
-        raise TypeError(f"{what}: a is {a.dtype}, b {b.dtype} (convert one of them: the merge compares keys of one type)")
-    if not a.is_cuda or not b.is_cuda:
-        raise ValueError(f"{what}: a and b must be device tensors (there is no CPU path)")
-    if a.dim() != 1 or b.dim() != 1 or b.device != a.device:
-        raise ValueError(f"{what}: a and b must be 1-D tensors on one device")
-    if (a_offsets is None) != (b_offsets is None):
-        raise ValueError(f"{what}: a_offsets and b_offsets must both be given or both be None")
-    for oname, o in (("a_offsets", a_offsets), ("b_offsets", b_offsets)):
-        if o is not None and (not torch.is_tensor(o) or o.dtype != torch.int64 or o.dim() != 1 or o.device != a.device):
-            raise ValueError(f"{what}: {oname} must be a 1-D int64 tensor on the keys' device")
-    if a_offsets is not None and a_offsets.numel() != b_offsets.numel():
-        raise ValueError(f"{what}: a_offsets and b_offsets must have the same number of entries")
-    if (payload_a is None) != (payload_b is None):
-        raise ValueError(f"{what}: payload_a and payload_b must both be given or both be None")
-    u32 = getattr(torch, "uint32", torch.int32)
-    for pname, p, k in (("payload_a", payload_a, a), ("payload_b", payload_b, b)):
-        if p is not None and (not torch.is_tensor(p) or p.shape != k.shape or p.device != k.device or p.dtype not in (torch.int32, u32)):
-            raise ValueError(f"{what}: {pname} must be an int32 / uint32 tensor shaped like its keys, on the same device")
-    if payload_a is not None and payload_a.dtype != payload_b.dtype:
-        raise ValueError(f"{what}: payload_a and payload_b must have one dtype")
+    name = _args.pair_key_name(what, a, b, "the merge compares keys of one type")
+    nseg = _args.check_pair(what, a, b, a_offsets, b_offsets)
+    _args.check_pair_payloads(what, a, b, payload_a, payload_b)
     na, nb = a.numel(), b.numel()
-    if na + nb > (1 << 31):
-        raise ValueError(f"{what}: at most 2^31 keys together (rsx_segmented_merge's bound)")
-    nseg = 1 if a_offsets is None else max(a_offsets.numel() - 1, 0)
+    _args.check_count(what, "rsx_segmented_merge", "keys together", na + nb)
     dev = a.device
     keys = torch.zeros(na + nb, dtype=a.dtype, device=dev)
     ooff = torch.zeros(nseg + 1, dtype=torch.int64, device=dev)
     pay = None if payload_a is None else torch.zeros(na + nb, dtype=payload_a.dtype, device=dev)
     index = torch.full((na + nb,), -1, dtype=torch.int32, device=dev) if want_index else None
     if na + nb > 0 and nseg > 0:
-        a_in, b_in = _aligned_copy(a, torch), _aligned_copy(b, torch)
-        cont = lambda t: None if t is None else t if t.is_contiguous() and t.data_ptr() % 8 == 0 else t.clone(memory_format=torch.contiguous_format)
+        ptr, cont = _args.ptr_nonempty, _args.as_offsets
+        a_in, b_in = _aligned_copy(a), _aligned_copy(b)
         ao, bo, pa, pb = cont(a_offsets), cont(b_offsets), cont(payload_a), cont(payload_b)
-        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-        device = dev.index if dev.index is not None else torch.cuda.current_device()
-        eng = _search_engine(device, torch.cuda.current_stream(dev).cuda_stream, name, bool(descending))
+        eng = _search_engine(*_args.device_and_stream(a), name, bool(descending))
         if pay is not None:             # (an empty side has no storage: any aligned address stands in for its payload, which is not read)
             pa_ptr, pb_ptr = (pa.data_ptr() if na else pay.data_ptr() + 4 * (na + nb)), (pb.data_ptr() if nb else pay.data_ptr() + 4 * (na + nb))
         else:
@@ -2287,21 +2155,18 @@ def segmented_merge(a, a_offsets, b, b_offsets, payload_a=None, payload_b=None, 
     return (k, oo) + ((p,) if p is not None else ()) + ((idx,) if return_index else ())
 
 
-def merge(a, b, payload_a=None, payload_b=None, descending: bool = False, return_index: bool = False):
-    """The stable merge of two sorted device tensors along their last dimension: 1-D inputs are one segment; N-D inputs with equal leading
-    shape are merged row by row, the rows being the segments of ONE rsx_segmented_merge call.  Returns keys of shape [..., La + Lb]
-    (with payloads: (keys, payload); with return_index=True the int64 positions in torch.cat([a, b], -1) of every output last).  Equal to
-    torch.sort(torch.cat([a, b], -1), dim=-1, stable=True, descending=descending) for rows sorted in this library's order (integer dtypes,
-    and floats without -0.0 and NaN, equal torch exactly).  Order, payloads and errors as segmented_merge."""
+def _pair_rows(what: str, a, b, payload_a=None, payload_b=None):
+    """The rows of two tensors with equal leading shape as the segments of a call with two sides: (a, a_offsets, b, b_offsets, payload_a,
+    payload_b), all flattened; 1-D inputs are one segment (offsets None)."""
     import torch
     for name, t in (("a", a), ("b", b)):
         if not torch.is_tensor(t):
-            raise TypeError(f"merge: {name} must be a tensor")
+            raise TypeError(f"{what}: {name} must be a tensor")
     if a.dim() == 0 or a.dim() != b.dim() or tuple(a.shape[:-1]) != tuple(b.shape[:-1]):
-        raise ValueError("merge: a and b must have the same number of dimensions (at least one) and equal leading shape")
+        raise ValueError(f"{what}: a and b must have the same number of dimensions (at least one) and equal leading shape")
     for pname, p, k in (("payload_a", payload_a, a), ("payload_b", payload_b, b)):
         if p is not None and (not torch.is_tensor(p) or p.shape != k.shape):
-            raise ValueError(f"merge: {pname} must be a tensor shaped like its keys")
+            raise ValueError(f"{what}: {pname} must be a tensor shaped like its keys")
     la, lb = a.shape[-1], b.shape[-1]
     flat = lambda t: None if t is None else t.contiguous().reshape(-1)
     ao = bo = None
@@ -2309,8 +2174,17 @@ def merge(a, b, payload_a=None, payload_b=None, descending: bool = False, return
         rows = a.numel() // la if la else (b.numel() // lb if lb else 0)
         steps = torch.arange(0, rows + 1, device=a.device, dtype=torch.int64)
         ao, bo = steps * la, steps * lb
-    k, _, p, idx = _merge_call("merge", flat(a), ao, flat(b), bo, flat(payload_a), flat(payload_b), descending, return_index)
-    shape = tuple(a.shape[:-1]) + (la + lb,)
+    return flat(a), ao, flat(b), bo, flat(payload_a), flat(payload_b)
+
+
+def merge(a, b, payload_a=None, payload_b=None, descending: bool = False, return_index: bool = False):
+    """The stable merge of two sorted device tensors along their last dimension: 1-D inputs are one segment; N-D inputs with equal leading
+    shape are merged row by row, the rows being the segments of ONE rsx_segmented_merge call.  Returns keys of shape [..., La + Lb]
+    (with payloads: (keys, payload); with return_index=True the int64 positions in torch.cat([a, b], -1) of every output last).  Equal to
+    torch.sort(torch.cat([a, b], -1), dim=-1, stable=True, descending=descending) for rows sorted in this library's order (integer dtypes,
+    and floats without -0.0 and NaN, equal torch exactly).  Order, payloads and errors as segmented_merge."""
+    k, _, p, idx = _merge_call("merge", *_pair_rows("merge", a, b, payload_a, payload_b), descending, return_index)
+    shape = tuple(a.shape[:-1]) + (a.shape[-1] + b.shape[-1],)
     res = (k.reshape(shape),) + ((p.reshape(shape),) if p is not None else ()) + ((idx.reshape(shape),) if return_index else ())
     return res[0] if len(res) == 1 else res
 
@@ -2331,40 +2205,14 @@ def _setop_call(what: str, a, a_offsets, b, b_offsets, op, payload_a, payload_b,
     """One rsx_segmented_set_op call on 1-D device tensors (both offsets None: one segment).  Returns (keys, out_offsets, payload, index,
     match), trimmed to out_offsets[-1] (ONE host synchronisation)."""
     import torch
-    for name, t in (("a", a), ("b", b)):
-        if not torch.is_tensor(t):
-            raise TypeError(f"{what}: {name} must be a tensor")
-    name = str(a.dtype).replace("torch.", "")
-    if name not in _KEY_DTYPES:
-        raise TypeError(f"{what}: unsupported key type {a.dtype}")
-    if b.dtype != a.dtype:
-        raise TypeError(f"{what}: a is {a.dtype}, b {b.dtype} (convert one of them: a set operation compares keys of one type)")
+    name = _args.pair_key_name(what, a, b, "a set operation compares keys of one type")
     code = _set_op_code(what, op)
     if want_match and code != SET_INTERSECTION:
         raise ValueError(f"{what}: return_match belongs to the intersection (no other op pairs its outputs with b)")
-    if not a.is_cuda or not b.is_cuda:
-        raise ValueError(f"{what}: a and b must be device tensors (there is no CPU path)")
-    if a.dim() != 1 or b.dim() != 1 or b.device != a.device:
-        raise ValueError(f"{what}: a and b must be 1-D tensors on one device")
-    if (a_offsets is None) != (b_offsets is None):
-        raise ValueError(f"{what}: a_offsets and b_offsets must both be given or both be None")
-    for oname, o in (("a_offsets", a_offsets), ("b_offsets", b_offsets)):
-        if o is not None and (not torch.is_tensor(o) or o.dtype != torch.int64 or o.dim() != 1 or o.device != a.device):
-            raise ValueError(f"{what}: {oname} must be a 1-D int64 tensor on the keys' device")
-    if a_offsets is not None and a_offsets.numel() != b_offsets.numel():
-        raise ValueError(f"{what}: a_offsets and b_offsets must have the same number of entries")
-    if (payload_a is None) != (payload_b is None):
-        raise ValueError(f"{what}: payload_a and payload_b must both be given or both be None")
-    u32 = getattr(torch, "uint32", torch.int32)
-    for pname, p, k in (("payload_a", payload_a, a), ("payload_b", payload_b, b)):
-        if p is not None and (not torch.is_tensor(p) or p.shape != k.shape or p.device != k.device or p.dtype not in (torch.int32, u32)):
-            raise ValueError(f"{what}: {pname} must be an int32 / uint32 tensor shaped like its keys, on the same device")
-    if payload_a is not None and payload_a.dtype != payload_b.dtype:
-        raise ValueError(f"{what}: payload_a and payload_b must have one dtype")
+    nseg = _args.check_pair(what, a, b, a_offsets, b_offsets)
+    _args.check_pair_payloads(what, a, b, payload_a, payload_b)
     na, nb = a.numel(), b.numel()
-    if na + nb > (1 << 31):
-        raise ValueError(f"{what}: at most 2^31 keys together (rsx_segmented_set_op's bound)")
-    nseg = 1 if a_offsets is None else max(a_offsets.numel() - 1, 0)
+    _args.check_count(what, "rsx_segmented_set_op", "keys together", na + nb)
     cap = na if code in (SET_INTERSECTION, SET_DIFFERENCE) else na + nb
     dev = a.device
     keys = torch.empty(cap, dtype=a.dtype, device=dev)
@@ -2374,12 +2222,10 @@ def _setop_call(what: str, a, a_offsets, b, b_offsets, op, payload_a, payload_b,
     match = torch.empty(cap, dtype=torch.int32, device=dev) if want_match else None
     total = 0
     if na + nb > 0 and nseg > 0:
-        a_in, b_in = _aligned_copy(a, torch), _aligned_copy(b, torch)
-        cont = lambda t: None if t is None else t if t.is_contiguous() and t.data_ptr() % 8 == 0 else t.clone(memory_format=torch.contiguous_format)
+        ptr, cont = _args.ptr_nonempty, _args.as_offsets
+        a_in, b_in = _aligned_copy(a), _aligned_copy(b)
         ao, bo, pa, pb = cont(a_offsets), cont(b_offsets), cont(payload_a), cont(payload_b)
-        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-        device = dev.index if dev.index is not None else torch.cuda.current_device()
-        eng = _search_engine(device, torch.cuda.current_stream(dev).cuda_stream, name, bool(descending))
+        eng = _search_engine(*_args.device_and_stream(a), name, bool(descending))
         spare = None
         if pay is not None:             # (an empty side or an empty output has no storage: a spare word stands in; it is neither read nor written)
             spare = torch.empty(4, dtype=torch.int32, device=dev)
@@ -2390,8 +2236,8 @@ def _setop_call(what: str, a, a_offsets, b, b_offsets, op, payload_a, payload_b,
                              d_a_payload=pa_ptr, d_b_payload=pb_ptr, d_payload_out=po_ptr)
         total = int(koff[-1].item())            # the one read-back (a host synchronisation): how many were kept
         eng.check_status()      # reports bad offsets of calls that have already finished
-    widen = lambda t: None if t is None else (t[:total].to(torch.int64) & 0xFFFFFFFF)
-    return keys[:total], koff, (None if pay is None else pay[:total]), widen(index), widen(match)
+    index, match = (None if t is None else _args.widen(t[:total]) for t in (index, match))
+    return keys[:total], koff, (None if pay is None else pay[:total]), index, match
 
 
 def segmented_set_op(a, a_offsets, b, b_offsets, op, payload_a=None, payload_b=None, descending: bool = False, return_index: bool = False,
@@ -2413,23 +2259,8 @@ def segmented_set_op(a, a_offsets, b, b_offsets, op, payload_a=None, payload_b=N
 
 
 def _set_rows(what: str, op: int, a, b, payload_a, payload_b, descending: bool, return_index: bool, return_match: bool):
-    import torch
-    for name, t in (("a", a), ("b", b)):
-        if not torch.is_tensor(t):
-            raise TypeError(f"{what}: {name} must be a tensor")
-    if a.dim() == 0 or a.dim() != b.dim() or tuple(a.shape[:-1]) != tuple(b.shape[:-1]):
-        raise ValueError(f"{what}: a and b must have the same number of dimensions (at least one) and equal leading shape")
-    for pname, p, k in (("payload_a", payload_a, a), ("payload_b", payload_b, b)):
-        if p is not None and (not torch.is_tensor(p) or p.shape != k.shape):
-            raise ValueError(f"{what}: {pname} must be a tensor shaped like its keys")
-    la, lb = a.shape[-1], b.shape[-1]
-    flat = lambda t: None if t is None else t.contiguous().reshape(-1)
-    ao = bo = None
-    if a.dim() > 1:
-        rows = a.numel() // la if la else (b.numel() // lb if lb else 0)
-        steps = torch.arange(0, rows + 1, device=a.device, dtype=torch.int64)
-        ao, bo = steps * la, steps * lb
-    k, oo, p, idx, mt = _setop_call(what, flat(a), ao, flat(b), bo, op, flat(payload_a), flat(payload_b), descending, return_index, return_match)
+    fa, ao, fb, bo, pa, pb = _pair_rows(what, a, b, payload_a, payload_b)
+    k, oo, p, idx, mt = _setop_call(what, fa, ao, fb, bo, op, pa, pb, descending, return_index, return_match)
     res = (k,) + ((oo,) if a.dim() > 1 else ()) + ((p,) if p is not None else ()) + ((idx,) if return_index else ()) + ((mt,) if return_match else ())
     return res[0] if len(res) == 1 else res
 
@@ -2477,49 +2308,26 @@ def _join_call(what: str, a, a_offsets, b, b_offsets, how, descending: bool, wan
     of the total, then the writing call into buffers of exactly that size.  capacity an int: one call, no synchronisation, buffers of that
     length holding -1 (keys: 0) behind min(total, capacity)."""
     import torch
-    for name, t in (("a", a), ("b", b)):
-        if not torch.is_tensor(t):
-            raise TypeError(f"{what}: {name} must be a tensor")
-    name = str(a.dtype).replace("torch.", "")
-    if name not in _KEY_DTYPES:
-        raise TypeError(f"{what}: unsupported key type {a.dtype}")
-    if b.dtype != a.dtype:
-        raise TypeError(f"{what}: a is {a.dtype}, b {b.dtype} (convert one of them: a join compares keys of one type)")
+    name = _args.pair_key_name(what, a, b, "a join compares keys of one type")
     code = _join_code(what, how)
-    if not a.is_cuda or not b.is_cuda:
-        raise ValueError(f"{what}: a and b must be device tensors (there is no CPU path)")
-    if a.dim() != 1 or b.dim() != 1 or b.device != a.device:
-        raise ValueError(f"{what}: a and b must be 1-D tensors on one device")
-    if (a_offsets is None) != (b_offsets is None):
-        raise ValueError(f"{what}: a_offsets and b_offsets must both be given or both be None")
-    for oname, o in (("a_offsets", a_offsets), ("b_offsets", b_offsets)):
-        if o is not None and (not torch.is_tensor(o) or o.dtype != torch.int64 or o.dim() != 1 or o.device != a.device):
-            raise ValueError(f"{what}: {oname} must be a 1-D int64 tensor on the keys' device")
-    if a_offsets is not None and a_offsets.numel() != b_offsets.numel():
-        raise ValueError(f"{what}: a_offsets and b_offsets must have the same number of entries")
+    nseg = _args.check_pair(what, a, b, a_offsets, b_offsets)
     if capacity is not None and (not isinstance(capacity, int) or isinstance(capacity, bool) or capacity < 0 or capacity > (1 << 34)):
         raise ValueError(f"{what}: capacity must be None or an int in [0, 2^34]")
     na, nb = a.numel(), b.numel()
-    if na > (1 << 31) or nb > (1 << 31):
-        raise ValueError(f"{what}: at most 2^31 keys in a and in b (rsx_segmented_join's bound)")
-    nseg = 1 if a_offsets is None else max(a_offsets.numel() - 1, 0)
+    _args.check_count(what, "rsx_segmented_join", "keys in a and in b", na, nb)
     dev = a.device
     ooff = torch.zeros(nseg + 1, dtype=torch.int64, device=dev)
     want_b = code != JOIN_ANTI
     eng = None
+    ptr = _args.ptr_nonempty
     if nseg > 0:
-        a_in, b_in = _aligned_copy(a, torch), _aligned_copy(b, torch)
-        cont = lambda t: None if t is None else t if t.is_contiguous() and t.data_ptr() % 8 == 0 else t.clone(memory_format=torch.contiguous_format)
-        ao, bo = cont(a_offsets), cont(b_offsets)
-        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-        device = dev.index if dev.index is not None else torch.cuda.current_device()
-        eng = _search_engine(device, torch.cuda.current_stream(dev).cuda_stream, name, bool(descending))
-        join = lambda cap, ko, io, bo_: eng.segmented_join(ptr(a_in), na, ptr(ao), ptr(b_in), nb, ptr(bo), nseg, code, cap, ooff.data_ptr(),
-                                                           d_a_index_out=ptr(io), d_b_index_out=ptr(bo_), d_keys_out=ptr(ko))
+        a_in, b_in, ao, bo = _aligned_copy(a), _aligned_copy(b), _args.as_offsets(a_offsets), _args.as_offsets(b_offsets)      # (alive until the calls are enqueued)
+        eng = _search_engine(*_args.device_and_stream(a), name, bool(descending))
+        sides = (ptr(a_in), na, ptr(ao), ptr(b_in), nb, ptr(bo))
     if capacity is None:
         cap = 0
         if eng is not None:
-            join(0, None, None, None)
+            eng.segmented_join(*sides, nseg, code, 0, ooff.data_ptr())
             cap = int(ooff[-1].item())          # the one read-back (a host synchronisation): how many rows there are
             eng.check_status()
             if cap > (1 << 34):
@@ -2531,10 +2339,9 @@ def _join_call(what: str, a, a_offsets, b, b_offsets, how, descending: bool, wan
     ib = torch.full((cap,), -1, dtype=torch.int32, device=dev) if want_b else None
     keys = torch.zeros(cap, dtype=a.dtype, device=dev) if want_keys else None
     if eng is not None and cap > 0:
-        join(cap, keys, ia, ib)
+        eng.segmented_join(*sides, nseg, code, cap, ooff.data_ptr(), d_a_index_out=ptr(ia), d_b_index_out=ptr(ib), d_keys_out=ptr(keys))
         eng.check_status()      # reports bad offsets of calls that have already finished; no synchronisation
-    widen = lambda t: None if t is None else torch.where(t == -1, t.to(torch.int64), t.to(torch.int64) & 0xFFFFFFFF)
-    return widen(ia), widen(ib), ooff, keys
+    return _args.widen_keeping_none(ia), _args.widen_keeping_none(ib), ooff, keys
 
 
 def segmented_join(a, a_offsets, b, b_offsets, how="inner", descending: bool = False, return_keys: bool = False, capacity=None):
@@ -2552,29 +2359,13 @@ def segmented_join(a, a_offsets, b, b_offsets, how="inner", descending: bool = F
     return (ia, ib, oo) + ((k,) if return_keys else ())
 
 
-def _join_rows(what: str, a, b):
-    import torch
-    for name, t in (("a", a), ("b", b)):
-        if not torch.is_tensor(t):
-            raise TypeError(f"{what}: {name} must be a tensor")
-    if a.dim() == 0 or a.dim() != b.dim() or tuple(a.shape[:-1]) != tuple(b.shape[:-1]):
-        raise ValueError(f"{what}: a and b must have the same number of dimensions (at least one) and equal leading shape")
-    la, lb = a.shape[-1], b.shape[-1]
-    ao = bo = None
-    if a.dim() > 1:
-        rows = a.numel() // la if la else (b.numel() // lb if lb else 0)
-        steps = torch.arange(0, rows + 1, device=a.device, dtype=torch.int64)
-        ao, bo = steps * la, steps * lb
-    return a.contiguous().reshape(-1), ao, b.contiguous().reshape(-1), bo
-
-
 def join_sorted(a, b, how="inner", descending: bool = False, capacity=None):
     """The equi-join of two sorted device tensors along their last dimension.  1-D inputs are one segment: (ia, ib) comes back, the
     positions in a and in b of every pair of equal keys (a[ia] == b[ib] bit for bit), ordered by ia, then ib.  N-D inputs with equal
     leading shape are joined row by row, the rows being the segments of one rsx_segmented_join, and (ia, ib, row_offsets) comes back:
     ia and ib are columns, and row r's pairs are [row_offsets[r] : row_offsets[r+1]).  how, capacity, order and errors as
     segmented_join."""
-    fa, ao, fb, bo = _join_rows("join_sorted", a, b)
+    fa, ao, fb, bo = _pair_rows("join_sorted", a, b)[:4]
     ia, ib, oo, _ = _join_call("join_sorted", fa, ao, fb, bo, how, descending, False, capacity)
     return (ia, ib) + ((oo,) if a.dim() > 1 else ())
 
@@ -2584,7 +2375,7 @@ def isin_sorted(a, b, invert: bool = False, descending: bool = False):
     (in b's row of the same index for N-D inputs); invert=True: where it has none.  The semi (anti) join scattered to a mask; never
     synchronises with the host."""
     import torch
-    fa, ao, fb, bo = _join_rows("isin_sorted", a, b)
+    fa, ao, fb, bo = _pair_rows("isin_sorted", a, b)[:4]
     na = fa.numel() if torch.is_tensor(fa) else 0
     ia, _, oo, _ = _join_call("isin_sorted", fa, ao, fb, bo, JOIN_ANTI if invert else JOIN_SEMI, descending, False, na)
     mask = torch.zeros(na + 1, dtype=torch.bool, device=fa.device)

@@ -1,0 +1,160 @@
+"""The argument rules that the torch wrappers of the segmented family share, each written once.
+
+A wrapper in __init__.py checks its tensors, hands their addresses to ONE engine call and trims what comes back; this module owns the
+parts of that which do not depend on the call: dtype names and the two dtype tables, the offsets rule, the copies a misaligned or strided
+input needs, pointer-or-None, the device and stream of a tensor, the uint32-in-int32 widenings, the 2^31 guard, and the checks of a call
+with two sorted sides (merge, set_op, join).  Every message starts with the caller's `what` and takes the words that differ per call as
+arguments.  It knows nothing of Engine or ctypes and imports torch on first use."""
+from __future__ import annotations
+
+# dtype name -> (key bytes, RSX_KEY_* kind: 0 unsigned, 1 signed, 2 float)
+KEY_DTYPES = {"uint32": (4, 0), "int32": (4, 1), "uint64": (8, 0), "int64": (8, 1), "float32": (4, 2), "float64": (8, 2)}
+# dtype name -> RSX_VALUE_* kind
+VALUE_KINDS = {"int32": 0, "int64": 1, "float32": 2, "float64": 3}
+MAX_ELEMENTS = 1 << 31      # what one call of the family addresses
+
+_torch = None
+_DTYPE_NAMES: dict = {}
+
+
+def torch_module():
+    global _torch
+    if _torch is None:
+        import torch
+        _torch = torch
+    return _torch
+
+
+def dtype_name(t) -> str:
+    """'int32' for torch.int32"""
+    name = _DTYPE_NAMES.get(t.dtype)
+    if name is None:
+        name = _DTYPE_NAMES[t.dtype] = str(t.dtype).replace("torch.", "")
+    return name
+
+
+def key_name(what: str, keys) -> str:
+    """The dtype name of a key tensor, one of KEY_DTYPES."""
+    name = dtype_name(keys)
+    if name not in KEY_DTYPES:
+        raise TypeError(f"{what}: unsupported key type {keys.dtype}")
+    return name
+
+
+def value_kind(what: str, values) -> int:
+    """The RSX_VALUE_* kind of a value tensor."""
+    kind = VALUE_KINDS.get(dtype_name(values))
+    if kind is None:
+        raise TypeError(f"{what}: unsupported value type {values.dtype} (int32, int64, float32 or float64)")
+    return kind
+
+
+def check_offsets(what: str, offsets, device, name: str = "offsets", none_ok: bool = False, whose: str = "keys'", hint: str = "") -> None:
+    """offsets (the argument called `name`) are a 1-D int64 tensor on `device`, which the message calls the `whose` device; None passes
+    only where the caller says so."""
+    if offsets is None and none_ok:
+        return
+    torch = _torch or torch_module()
+    if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.device != device:
+        raise ValueError(f"{what}: {name} must be a 1-D int64 tensor on the {whose} device{hint}")
+
+
+def _contiguous_copy(t):
+    return t.clone(memory_format=torch_module().contiguous_format)
+
+
+def as_offsets(t):
+    """t itself when contiguous and 8-byte aligned, else a contiguous copy; None stays None.  (Also the 32-bit payloads of merge and set_op.)"""
+    if t is None or (t.is_contiguous() and t.data_ptr() % 8 == 0):
+        return t
+    return _contiguous_copy(t)
+
+
+def aligned_copy(t):
+    """t itself when contiguous and 16-byte aligned, else a fresh contiguous copy (torch allocations are aligned)."""
+    if t.is_contiguous() and t.data_ptr() % 16 == 0:
+        return t
+    return _contiguous_copy(t)
+
+
+def ptr(t):
+    """the address of a tensor, None for None"""
+    return None if t is None else t.data_ptr()
+
+
+def ptr_nonempty(t):
+    """the address of a tensor, None for None and for a tensor without elements (which has no storage to speak of)"""
+    return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
+def device_and_stream(t) -> tuple:
+    """(device index, handle of torch's current stream on that device) of a device tensor: what an engine is looked up by"""
+    torch = _torch or torch_module()
+    dev = t.device
+    return (dev.index if dev.index is not None else torch.cuda.current_device()), torch.cuda.current_stream(dev).cuda_stream
+
+
+def widen(t):
+    """a uint32 result held in an int32 tensor as int64; None stays None"""
+    return None if t is None else t.to(torch_module().int64) & 0xFFFFFFFF
+
+
+def widen_keeping_none(t):
+    """widen, for the join's indices: 0xFFFFFFFF means "none" and stays -1"""
+    if t is None:
+        return None
+    torch = torch_module()
+    wide = t.to(torch.int64)
+    return torch.where(t == -1, wide, wide & 0xFFFFFFFF)
+
+
+def check_count(what: str, call: str, things: str, *counts) -> None:
+    """the family's bound of 2^31 on every one of `counts`; `things` is what the message says there are too many of"""
+    for n in counts:
+        if n > MAX_ELEMENTS:
+            raise ValueError(f"{what}: at most 2^31 {things} ({call}'s bound)")
+
+
+# -- calls with two sorted sides a and b: merge, set_op, join ---------------------------------------------------------------------------
+def pair_key_name(what: str, a, b, phrase: str) -> str:
+    """Both sides are tensors of one key type: its name.  `phrase` says who compares them, e.g. "the merge compares keys of one type"."""
+    is_tensor = torch_module().is_tensor
+    for name, t in (("a", a), ("b", b)):
+        if not is_tensor(t):
+            raise TypeError(f"{what}: {name} must be a tensor")
+    key = key_name(what, a)
+    if b.dtype != a.dtype:
+        raise TypeError(f"{what}: a is {a.dtype}, b {b.dtype} (convert one of them: {phrase})")
+    return key
+
+
+def check_pair(what: str, a, b, a_offsets, b_offsets) -> int:
+    """Both sides are 1-D tensors on one device, with offsets for both or for neither, of equal length: the number of segments."""
+    if not a.is_cuda or not b.is_cuda:
+        raise ValueError(f"{what}: a and b must be device tensors (there is no CPU path)")
+    if a.dim() != 1 or b.dim() != 1 or b.device != a.device:
+        raise ValueError(f"{what}: a and b must be 1-D tensors on one device")
+    if (a_offsets is None) != (b_offsets is None):
+        raise ValueError(f"{what}: a_offsets and b_offsets must both be given or both be None")
+    if a_offsets is None:
+        return 1
+    check_offsets(what, a_offsets, a.device, "a_offsets")
+    check_offsets(what, b_offsets, a.device, "b_offsets")
+    if a_offsets.numel() != b_offsets.numel():
+        raise ValueError(f"{what}: a_offsets and b_offsets must have the same number of entries")
+    return max(a_offsets.numel() - 1, 0)
+
+
+def check_pair_payloads(what: str, a, b, payload_a, payload_b) -> None:
+    """The 32-bit words that travel with the keys of merge and set_op: for both sides or for neither, shaped like their keys, of one dtype."""
+    if (payload_a is None) != (payload_b is None):
+        raise ValueError(f"{what}: payload_a and payload_b must both be given or both be None")
+    if payload_a is None:
+        return
+    torch = torch_module()
+    words = (torch.int32, getattr(torch, "uint32", torch.int32))
+    for pname, p, k in (("payload_a", payload_a, a), ("payload_b", payload_b, b)):
+        if not torch.is_tensor(p) or p.shape != k.shape or p.device != k.device or p.dtype not in words:
+            raise ValueError(f"{what}: {pname} must be an int32 / uint32 tensor shaped like its keys, on the same device")
+    if payload_a.dtype != payload_b.dtype:
+        raise ValueError(f"{what}: payload_a and payload_b must have one dtype")
