@@ -134,13 +134,14 @@ def sparse_large_bad(seed: int = 1):
 # -- 3. more segments of class 1 / class 2 than workgroups ---------------------------------------------------------------------------------
 
 def stride_layout(cls: int, cus: int = CUS, seed: int = 0):
-    """16 * cus + 400 segments of 257..1024 keys (cls 1) or 4 * cus + 200 of 1025..4096 keys (cls 2), contiguous from off[0] = 1.
-    Wherever a workgroup has a second item (item i + grid after item i), the second one is the shorter of the two, so its pads lie over
-    the image of a longer segment.  Path: trips[cls] >= 2.  Returns (n, off); few_distinct() makes the keys."""
+    """32 * cus + 400 segments of 2..256 keys (cls 0), 16 * cus + 400 of 257..1024 keys (cls 1) or 4 * cus + 200 of 1025..4096 keys
+    (cls 2), contiguous from off[0] = 1.  Wherever a workgroup has a second item (item i + grid after item i), the second one is the
+    shorter of the two, so its pads lie over the image of a longer segment.  Path: trips[cls] >= 2.  Returns (n, off); few_distinct()
+    makes the keys.  (Class 0 serves the selects' LDS sorts; the segmented sort's own tests run classes 1 and 2.)"""
     rng = np.random.default_rng(300 + seed + cls)
-    lo, hi = (CLASS0_MAX + 1, CLASS1_MAX) if cls == 1 else (CLASS1_MAX + 1, TILE)
+    lo, hi = ((2, CLASS0_MAX), (CLASS0_MAX + 1, CLASS1_MAX), (CLASS1_MAX + 1, TILE))[cls]
     grid = cus * PER_CU[cls]
-    extra = 400 if cls == 1 else 200
+    extra = 200 if cls == 2 else 400
     lens = rng.integers(lo, hi, grid + extra, endpoint=True)
     first, second = lens[:extra].copy(), lens[grid:].copy()
     lens[:extra] = np.maximum(np.maximum(first, second), lo + 1)

@@ -5,7 +5,9 @@ The referee is tests/_wselect_ref.py: the stable argsort of the order-mapped key
 searchsorted, compared bit for bit: keys, positions, ranks, masses and totals.  The outputs start out holding a sentinel that must
 survive in every slot the call may not write (targets without an answer, rows of invalid segments) and sit inside guard bands that must
 come back untouched.  Lengths reach every path: empty and one-key segments, the three LDS classes (<= 256, <= 1024, <= 4096 keys) and
-the select chain over the tiles of larger segments, with several large segments in one group of tiles.
+the select chain over the tiles of larger segments.  Every layout here runs the chain with one tile per group and at most one item per
+workgroup in every kernel; groups shared by several large segments, the grid strides and segments of more than 1024 tiles are the
+business of tests/test_gpu_wselect_paths.py.
 """
 import numpy as np
 import pytest

@@ -1,7 +1,8 @@
 """CPU checks of the weighted select (rsx_segmented_weighted_select): header, binding and exports agree; the referee of the GPU tests
 (tests/_wselect_ref.py) against brute force with Python integers and against the two chains the call replaces; the mass function and
 the target rule of csrc/rsx_mass_math.hpp — what the kernels call — through the stand-alone wselect_selftest, plain and under
--fsanitize=address,undefined, against the numpy form; and the torch wrappers' refusals on host tensors."""
+-fsanitize=address,undefined, against the numpy form; the torch wrappers' refusals on host tensors; and the launch geometry at 256 CUs of
+the layouts that tests/test_gpu_wselect_paths.py runs: each one still reaches the path it is there for."""
 import ctypes as C
 import os
 import re
@@ -10,6 +11,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import _segmented_ref as S
+import _wselect_ref as W
 from _wselect_ref import MASS_ONE, brute_force, mass_np, target_of, wselect_oracle
 from test_gpu_float_keys import special
 
@@ -216,3 +219,92 @@ def test_selftest_refuses_bad_cases(tmp_path):
         path = tmp_path / "bad.txt"
         path.write_text(text)
         assert subprocess.run([SELFTESTS["plain"], str(path)], capture_output=True).returncode == 1, text
+
+
+# -- the layouts of tests/test_gpu_wselect_paths.py reach their paths at 256 CUs ----------------------------------------------------------------
+
+def test_geometry_hand_made_case():
+    """Four segments from 3, three of them large; every figure below is worked out by hand from the offsets."""
+    off = S.offsets_from([5000, 9000, 300, 4097], start=3)              # 3, 5003, 14003, 14303, 18400
+    n = int(off[-1]) + 5                                                # 18405
+    # seg_shape: max_large = min(4, 18405 / 4097) = 4, max_tiles = ceil(18405 / 4096) + 4 = 9.  Tiles on the 4096-key grid: [3, 5003) 2,
+    # [5003, 14003) grid tiles 1..3: 3, [14303, 18400) grid tiles 3..4: 2; tstart = 0, 2, 5, 7
+    g = W.wselect_geometry(off, n, 3, cus=1)                            # 8 groups wanted: gtiles = ceil(9 / 8) = 2
+    assert (g["gtiles"], g["groups"], g["switches"]) == (2, 5, 1)       # tstart 5 is odd: segment 3 begins inside group 2
+    assert (g["nlarge"], g["items"], g["pick_grid"]) == (3, 9, 2) and (g["tiles"], g["tie_grid"], g["max_segment_tiles"]) == (7, 8, 3)
+    assert g["count"] == [0, 1, 0] and g["sort_grid"] == [4, 4, 4] and g["trips"] == [0, 1, 0]
+    g = W.wselect_geometry(off, n, 4)
+    assert (g["gtiles"], g["groups"], g["switches"], g["items"], g["pick_grid"], g["tie_grid"]) == (1, 9, 0, 12, 16, 9)
+    assert W.answer_tiles(off, 1, [0, 3188, 3189, 8999]) == [0, 0, 1, 2]      # 5003 = 4096 + 907: 3189 keys in its first tile
+    assert W.answer_tiles(off, 0, [4092, 4093]) == [0, 1]
+    assert "gtiles=1" in W.summary(g) and "items=12/16" in W.summary(g)
+
+
+def test_the_first_suite_stays_on_one_group_and_one_trip():
+    """The state the path tests were written against: the LENGTHS layout of tests/test_gpu_wselect.py runs one tile per group, no
+    workgroup of any kernel takes a second item, and no segment has more than one chunk of tiles.  If the sizing formulas of
+    capi_wselect.inc change, this and the layout tests below fail first."""
+    from test_gpu_wselect import LENGTHS
+    off = S.offsets_from(LENGTHS, start=3)
+    g = W.wselect_geometry(off, int(off[-1]) + 5, 4)
+    print(W.summary(g))
+    assert g["gtiles"] == 1 and g["switches"] == 0 and max(g["trips"]) <= 1
+    assert g["items"] <= g["pick_grid"] and g["tiles"] <= g["tie_grid"] and g["max_segment_tiles"] <= W.FIND_CHUNK
+
+
+def test_layout_many_large_shares_groups_and_strides():
+    """many_large: gtiles >= 2 with at least `cus` large segments beginning inside a group; at R = 4 more than twice as many items as
+    workgroups on the pick grid; more tiles than workgroups on the tie grid; at every R at least a second item per workgroup"""
+    n, off = W.many_large()
+    lens = np.diff(off.astype(np.int64))
+    assert int(off[0]) == 3 and n == int(off[-1]) + 5 and np.count_nonzero(lens > W.TILE) == 4 * W.CUS and lens.max() <= 8000
+    assert set(lens[lens <= W.TILE].tolist()) == set(W.MANY_SMALL) and n < 6500000
+    g = W.wselect_geometry(off, n, 4)
+    print(W.summary(g))
+    assert g["gtiles"] >= 2 and g["switches"] >= W.CUS and g["items"] > 2 * g["pick_grid"] and g["tiles"] > g["tie_grid"]
+    for R in (1, 2, 3):
+        g = W.wselect_geometry(off, n, R)
+        assert g["gtiles"] >= 2 and g["items"] >= 2 * g["pick_grid"]
+
+
+@pytest.mark.parametrize("cus", [256, 304, 64])
+@pytest.mark.parametrize("cls", [0, 1, 2])
+def test_layout_stride_reaches_the_second_item_of_every_class(cls, cus):
+    """stride_layout: trips[cls] >= 2 for the selects' LDS sorts too, and every second item is the shorter one; the layouts of classes 1
+    and 2 are those the segmented sort's tests have always run"""
+    n, off = S.stride_layout(cls, cus)
+    g = W.wselect_geometry(off, n, 4, cus)
+    print(W.summary(g))
+    assert g["trips"][cls] >= 2 and g["count"][cls] > g["sort_grid"][cls] == cus * S.PER_CU[cls] and W.second_items_are_shorter(g, off, cls)
+    assert g["nlarge"] == 0 and sum(g["count"]) == g["count"][cls] == len(off) - 1
+    lens = np.diff(off.astype(np.int64))
+    assert lens.min() >= S.MIN_LEN[cls] and lens.max() <= (S.CLASS0_MAX, S.CLASS1_MAX, S.TILE)[cls]
+    if cus == 256 and cls:
+        assert (n, int(off.sum())) == {1: (2900122, 6722358991), 2: (3129694, 2032199116)}[cls]
+
+
+def test_layout_long_segment_has_a_second_chunk():
+    n, off = W.long_segment()
+    g = W.wselect_geometry(off, n, 4)
+    print(W.summary(g))
+    assert g["max_segment_tiles"] == 1031 > W.FIND_CHUNK and g["nlarge"] == 3 and int(off[0]) == 3
+    assert W.long_targets(1030) == [1025, 515, 1025, 1]
+
+
+def test_exponent_cases_reach_both_ends_of_the_mass_function():
+    """exponent_cases: at least ten of the sixteen have an answer, a segment weighs nothing in one, every positive weight is saturated in
+    another, and between the ends the masses take every size"""
+    answered = zero_total = all_saturated = 0
+    bits = set()
+    for dtype, wexp, off, w in W.exponent_cases():
+        assert w.dtype == dtype and np.isnan(w).any() and np.isinf(w).any() and (w < 0).any() and not np.isposinf(w[:int(off[1])]).any()
+        tiny = np.finfo(dtype).tiny
+        assert ((w > 0) & (w < tiny)).any()                                             # denormals
+        m = mass_np(w, wexp)
+        totals = [int(m[int(a):int(b)].sum()) for a, b in zip(off[:-1], off[1:])]
+        answered += any(totals)
+        zero_total += 0 in totals
+        all_saturated += bool((m[w > 0] == MASS_ONE).all())
+        bits |= {int(v).bit_length() for v in m[(m > 0) & (m < MASS_ONE)]}
+    assert answered >= 10 and zero_total >= 1 and all_saturated >= 1
+    assert bits == set(range(1, 32))
