@@ -712,6 +712,45 @@ int rsx_segmented_set_op(rsx_engine* e, const void* d_a, const uint32_t* d_a_pay
 int rsx_segmented_histogram(rsx_engine* e, const void* d_keys, uint64_t n, const uint64_t* d_offsets /* or NULL */, uint64_t num_segments,
                             const void* d_edges /* or NULL */, uint64_t lo_bits, uint64_t hi_bits, uint32_t width_shift, uint64_t num_bins,
                             uint32_t flags /* must be 0 */, uint32_t* d_counts_out);
+/* rsx_segmented_weighted_histogram: the MASSES of the keys of every segment summed per bin, bitwise reproducibly (torch.bincount(x,
+ *   weights=w), torch.histogram(x, bins, weight=w), numpy.histogram(weights=), the gate mass per expert of a router, with ragged rows).
+ *   RESULT.  d_sums_out holds S x B 64-bit sums, row-major: d_sums_out[s * B + b] = the sum of the masses of the keys of segment s that fall
+ *   into bin b.  THE BIN OF A KEY is exactly rsx_segmented_histogram's, in all three forms (edges, even integer, even float), with the
+ *   same parameters (d_edges, lo_bits, hi_bits, width_shift, num_bins), the engine's direction, totalOrder, the closed last bin and the
+ *   dropped keys: read them above.  d_weights holds n weights of weight_kind, element i beside key i; it is required (keys as their own
+ *   weights are not offered here).
+ *   MASS, flags == 0.  Exactly rsx_segmented_weighted_select's: RSX_WEIGHT_UINT32: the stored word, any uint32, weight_exp must be 0;
+ *   RSX_WEIGHT_FLOAT32 / _FLOAT64: mass(w) = 0 unless w > 0 (NaN, negatives and both zeros weigh nothing), else min(floor(w *
+ *   2^(31 - weight_exp)), 2^31), |weight_exp| <= 2048.  The sums are uint64.  The row sum of a histogram whose bins cover every key equals
+ *   that call's d_total_out[s] bit for bit.
+ *   MASS, RSX_WHIST_SIGNED in flags (float kinds only).  The mass is that of |w| — the sign bit cleared, then the rule above — and it is
+ *   added NEGATED for a negative weight: NaN of either sign and both zeros weigh nothing, -inf weighs -2^31.  The sums are then
+ *   two's-complement int64.
+ *   REPRODUCIBLE.  A weight is quantised once to an integer mass and every sum is a 64-bit integer add modulo 2^64: the adds commute, so
+ *   the result does not depend on their order, the grid, the stream, or eager or captured execution.  n <= 2^31 and a mass of at most
+ *   2^32 - 1 keep every sum below 2^63 in magnitude.
+ *   HOW.  One kernel zeroes the sums; one kernel walks tiles of 4096 keys with the thread's 16 weights loaded beside its keys (16-byte
+ *   loads where d_weights is 16-byte aligned).  Up to 2048 bins a workgroup sums in LDS (64-bit counters, a copy per wave up to 512
+ *   bins), keeps summing from tile to tile while the segment stays the same, and adds its non-zero sums to the result when the segment
+ *   changes and at its end.  More bins (the edges form takes up to 4096, its edges staged in LDS), and the pieces of segments shorter than
+ *   256 keys, add to the result directly.  A key whose mass is 0 adds nothing.  Bytes: n keys and n weights read, 16 per sum.
+ *   EVERYTHING ELSE is rsx_segmented_histogram's contract: d_offsets == NULL is the one segment [0, n); every one of the S * B sums is
+ *   written by every accepted call that launches, zeros included; n == 0 with a valid shape still zeroes; d_offsets != NULL with
+ *   num_segments == 0 returns RSX_OK and writes nothing.  THE ENGINE'S SORT STATE IS UNTOUCHED, whatever the engine's has_payload: n may
+ *   exceed the capacity and an earlier sort's result stays valid; no scratch grows.  Asynchronous on the engine's stream, nothing read
+ *   back, capturable once the engine's status words exist.  Offsets are validated on the device: with a bad segment all S * B sums are zero
+ *   and the next rsx_sync / rsx_check_status reports RSX_CALCULATION_FAILED once, naming this call and the first such segment; the
+ *   engine stays usable.
+ *   REFUSED AT ONCE: RSX_CALCULATION_FAILED for a null engine, flag bits other than RSX_WHIST_SIGNED, RSX_WHIST_SIGNED with
+ *   RSX_WEIGHT_UINT32, a weight_kind above RSX_WEIGHT_FLOAT64, weight_exp != 0 with RSX_WEIGHT_UINT32 or beyond +-2048, num_bins == 0,
+ *   more than 4096 bins in the edges form, the parameter combinations rsx_segmented_histogram rules out, 2^32 - 1 segments or more,
+ *   n > 2^31, num_segments * num_bins > 2^30; RSX_HOST_BUFFERS_FAILED for a null d_keys with n > 0 or one that is not 16-byte aligned, a
+ *   null d_weights or one not aligned to its element, edges not aligned to the key size, a null d_sums_out or one not 8-byte aligned,
+ *   offsets not 8-byte aligned, the sums overlapping an input, anything overlapping the engine's buffers. */
+#define RSX_WHIST_SIGNED 256      /* flags bit 8 (bits 0-7 are taken): float weights carry their sign, the sums are int64 */
+int rsx_segmented_weighted_histogram(rsx_engine* e, const void* d_keys, const void* d_weights, uint64_t n, const uint64_t* d_offsets /* or NULL */,
+                                     uint64_t num_segments, const void* d_edges /* or NULL */, uint64_t lo_bits, uint64_t hi_bits, uint32_t width_shift,
+                                     uint64_t num_bins, uint32_t flags, uint32_t weight_kind, int32_t weight_exp, uint64_t* d_sums_out);
 /* rsx_segmented_reduce: SUM, MIN, MAX, ARGMIN or ARGMAX of the values of every segment (cub::DeviceSegmentedReduce; torch.segment_reduce;
  *   x.sum(-1), amax, argmax over the rows of a batch).  Nothing is sorted and there are no keys: the engine's key kind does not matter.
  *   RESULT.  d_values_out[s] = op over v[off[s] .. off[s+1]) for EVERY s < S: dense by segment id, not packed.  d_offsets == NULL is the

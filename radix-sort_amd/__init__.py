@@ -48,6 +48,7 @@ COMPACT_PARTITION, COMPACT_INVERT, COMPACT_STRICT = 8, 16, 32                  #
 EXPAND_GATHER = 64         # RSX_EXPAND_GATHER: flags bit 6 of rsx_segmented_expand
 WSELECT_FRACTION = 128     # RSX_WSELECT_FRACTION: flags bit 7 of rsx_segmented_weighted_select
 WEIGHT_UINT32, WEIGHT_FLOAT32, WEIGHT_FLOAT64 = 0, 1, 2                        # RSX_WEIGHT_*: its weight kinds
+WHIST_SIGNED = 256         # RSX_WHIST_SIGNED: flags bit 8 of rsx_segmented_weighted_histogram
 SET_INTERSECTION, SET_DIFFERENCE, SET_UNION, SET_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3       # RSX_SET_*: op of rsx_segmented_set_op
 JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = 0, 1, 2, 3                                 # RSX_JOIN_*: op of rsx_segmented_join
 # rsx_experimental_option (include/radixsort_hip_experiments.h): known to the EXPERIMENTS build only (experiments()); the product library refuses them
@@ -60,7 +61,7 @@ SYMBOLS = [
     "rsx_create", "rsx_destroy", "rsx_set_stream", "rsx_get_stream", "rsx_set_option", "rsx_get_geometry", "rsx_resize",
     "rsx_upload", "rsx_fill_pad", "rsx_download", "rsx_pin_host", "rsx_unpin_host", "rsx_pipeline_submit", "rsx_pipeline_wait", "rsx_host_device_pointer",
     "rsx_histogram", "rsx_scan", "rsx_paste", "rsx_reorder", "rsx_sort", "rsx_sync", "rsx_check_status",
-    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_weighted_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_segmented_merge", "rsx_segmented_set_op", "rsx_segmented_histogram", "rsx_segmented_reduce", "rsx_segmented_expand", "rsx_segmented_join", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
+    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_weighted_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_segmented_merge", "rsx_segmented_set_op", "rsx_segmented_histogram", "rsx_segmented_weighted_histogram", "rsx_segmented_reduce", "rsx_segmented_expand", "rsx_segmented_join", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
 ]
 
 
@@ -177,6 +178,7 @@ def load_library() -> C.CDLL:
         "rsx_segmented_merge": ([P, P, P, U64, P, P, P, U64, P, U64, C.c_uint32, P, P, P, P], I),
         "rsx_segmented_set_op": ([P, P, P, U64, P, P, P, U64, P, U64, C.c_uint32, C.c_uint32, P, P, P, P, P], I),
         "rsx_segmented_histogram": ([P, P, U64, P, U64, P, U64, U64, C.c_uint32, U64, C.c_uint32, P], I),
+        "rsx_segmented_weighted_histogram": ([P, P, P, U64, P, U64, P, U64, U64, C.c_uint32, U64, C.c_uint32, C.c_uint32, C.c_int32, P], I),
         "rsx_segmented_reduce": ([P, P, U64, P, U64, C.c_uint32, C.c_uint32, C.c_uint32, P, P], I),
         "rsx_segmented_expand": ([P, P, U64, C.c_uint32, P, U64, U64, P, C.c_uint32, P, P, P], I),
         "rsx_segmented_join": ([P, P, U64, P, P, U64, P, U64, C.c_uint32, C.c_uint32, U64, P, P, P, P], I),
@@ -669,6 +671,23 @@ class Engine:
         self._check(self.lib.rsx_segmented_histogram(
             self._h, _opt(d_keys), n, _opt(d_offsets), num_segments, _opt(d_edges), self.key_bits(lo) if even else int(lo),
             self.key_bits(hi) if even else int(hi), width_shift, num_bins, 0, _opt(d_counts_out)), "rsx_segmented_histogram")
+
+    def segmented_weighted_histogram(self, d_keys: int | None, d_weights: int | None, n: int, d_offsets: int | None, num_segments: int, num_bins: int,
+                                     d_sums_out: int, weight_kind: int, weight_exp: int = 0, flags: int = 0, d_edges: int | None = None, lo=0, hi=0,
+                                     width_shift: int = 0) -> None:
+        """The MASSES of the keys of every segment [off[s], off[s+1]) summed per bin into d_sums_out (num_segments x num_bins 64-bit words,
+        row-major; the call zeroes them itself).  The bin of a key is segmented_histogram's (d_edges, lo, hi, width_shift, num_bins as
+        there).  d_weights: n weights of weight_kind (WEIGHT_UINT32: raw masses, weight_exp 0; WEIGHT_FLOAT32 / WEIGHT_FLOAT64: w > 0
+        weighs min(floor(w * 2^(31 - weight_exp)), 2^31), everything else nothing — segmented_weighted_select's rule).  flags
+        WHIST_SIGNED (float kinds): the mass of |w|, added negated for a negative weight; the sums are then int64.  All sums are 64-bit
+        integer adds: bitwise reproducible.  d_offsets None: ONE segment [0, n).  n may exceed the capacity and the engine's sort result
+        is left alone.  Asynchronous on the engine's stream; bad offsets (every sum is zero then) are reported by the next sync() /
+        check_status()."""
+        even = not d_edges
+        self._check(self.lib.rsx_segmented_weighted_histogram(
+            self._h, _opt(d_keys), _opt(d_weights), n, _opt(d_offsets), num_segments, _opt(d_edges), self.key_bits(lo) if even else int(lo),
+            self.key_bits(hi) if even else int(hi), width_shift, num_bins, flags, weight_kind, weight_exp, _opt(d_sums_out)),
+            "rsx_segmented_weighted_histogram")
 
     # -- exchange step of the sharded sort on the top B <= 8 bits ----------------
     def msd_count(self, d_keys: int, n: int, bits: int, world: int, d_counts: int) -> None:
@@ -2136,9 +2155,9 @@ _INT_KEY_DTYPES = ("uint32", "int32", "uint64", "int64")
 _HIST_MAX_COUNTERS = 1 << 31
 
 
-def _hist_call(what: str, keys, offsets, nseg: int, bins, lo, hi, width_shift: int, descending: bool):
-    """One rsx_segmented_histogram call on a 1-D device tensor (offsets None: one segment): the counters as an int64 tensor [nseg, B].
-    bins: an int (even form) or a 1-D tensor of B + 1 edges of the keys' dtype.  Reads nothing back."""
+def _hist_bins(what: str, keys, bins, lo, hi, width_shift: int):
+    """The key and bin arguments that the histogram and the weighted histogram share, checked in one order: (dtype name, edges or None,
+    B, lo, hi).  bins: an int (even form) or a 1-D tensor of B + 1 edges of the keys' dtype."""
     import torch
     name = _compact_keys_check(what, keys)
     edges = None
@@ -2163,6 +2182,14 @@ def _hist_call(what: str, keys, offsets, nseg: int, bins, lo, hi, width_shift: i
             lo = 0 if lo is None else lo
         elif lo is None or hi is None:
             raise ValueError(f"{what}: float keys need lo and hi in the even form")
+    return name, edges, nb, lo, hi
+
+
+def _hist_call(what: str, keys, offsets, nseg: int, bins, lo, hi, width_shift: int, descending: bool):
+    """One rsx_segmented_histogram call on a 1-D device tensor (offsets None: one segment): the counters as an int64 tensor [nseg, B].
+    bins: an int (even form) or a 1-D tensor of B + 1 edges of the keys' dtype.  Reads nothing back."""
+    import torch
+    name, edges, nb, lo, hi = _hist_bins(what, keys, bins, lo, hi, width_shift)
     n = keys.numel()
     if n > _args.MAX_ELEMENTS or nseg * nb > _HIST_MAX_COUNTERS:
         raise ValueError(f"{what}: at most 2^31 elements and 2^31 counters (rsx_segmented_histogram's bounds)")
@@ -2193,6 +2220,87 @@ def segmented_histogram(keys, offsets, bins, lo=None, hi=None, width_shift: int 
     return _hist_call("segmented_histogram", keys, offsets, nseg, bins, lo, hi, width_shift, descending)
 
 
+_WHIST_MAX_SUMS = 1 << 30
+
+
+def _whist_weight_type(what: str, weights) -> int:
+    """the weights are a tensor of a weight dtype (TypeError, with _tensor_args' wording): the RSX_WEIGHT_* kind"""
+    import torch
+    if not torch.is_tensor(weights):
+        raise TypeError(f"{what}: the weights must be a tensor")
+    return _args.weight_kind(what, weights)
+
+
+def _whist_scale(sums, k: int):
+    """sums (int64) * 2^k as float64: one rounding, in the conversion, and only from 2^53 units on; the scaling is exact"""
+    import math
+    import torch
+    out = sums.to(torch.float64)
+    while k:
+        step = max(min(k, 1000), -1000)
+        out = out * math.ldexp(1.0, step)
+        k -= step
+    return out
+
+
+def _whist_call(what: str, keys, offsets, nseg: int, weights, bins, lo, hi, width_shift: int, descending: bool, weight_max, signed: bool,
+                return_mass: bool):
+    """One rsx_segmented_weighted_histogram call on 1-D device tensors (offsets None: one segment): [nseg, B], float64 sums of the
+    weights as quantised (mass * 2^(e - 31)), or the int64 masses (return_mass, and integer weights).  weight_max None reads the largest
+    |weight| back once; otherwise nothing is read back."""
+    import torch
+    kind = _whist_weight_type(what, weights)
+    name, edges, nb, lo, hi = _hist_bins(what, keys, bins, lo, hi, width_shift)
+    if not weights.is_cuda or weights.device != keys.device:
+        raise ValueError(f"{what}: the weights must be a device tensor on the keys' device (there is no CPU path)")
+    if weights.shape != keys.shape:
+        raise ValueError(f"{what}: the weights must be shaped like the keys: one weight per key")
+    n = keys.numel()
+    if n > _args.MAX_ELEMENTS or nseg * nb > _WHIST_MAX_SUMS:
+        raise ValueError(f"{what}: at most 2^31 elements and 2^30 sums (rsx_segmented_weighted_histogram's bounds)")
+    wexp, flags = 0, 0
+    if kind != WEIGHT_UINT32:
+        if weight_max is None:
+            weight_max = float(weights.abs().amax().item()) if n else 0.0       # the one read-back
+        wexp = _weight_exp_of(float(weight_max))
+        flags = WHIST_SIGNED if signed else 0
+    sums = torch.zeros((nseg, nb), dtype=torch.int64, device=keys.device)
+    if nseg > 0 and n > 0:
+        k_in = _aligned_copy(keys)
+        w_in = weights.contiguous()
+        off = _args.as_offsets(offsets)
+        eng = _search_engine(*_args.device_and_stream(keys), name, bool(descending))
+        eng.segmented_weighted_histogram(k_in.data_ptr(), w_in.data_ptr(), n, _args.ptr(off), nseg, nb, sums.data_ptr(), kind, wexp, flags,
+                                         d_edges=_args.ptr(edges), lo=lo or 0, hi=hi or 0, width_shift=int(width_shift))
+        eng.check_status()      # reports bad offsets of calls that have already finished; no synchronisation
+    if return_mass or kind == WEIGHT_UINT32:
+        return sums
+    return _whist_scale(sums, wexp - 31)
+
+
+def segmented_weighted_histogram(keys, offsets, weights, bins, lo=None, hi=None, width_shift: int = 0, descending: bool = False, weight_max=None,
+                                 signed: bool = True, return_mass: bool = False):
+    """The WEIGHTS of the keys of every segment [offsets[s], offsets[s+1]) of the 1-D device tensor `keys` summed per bin in ONE engine call
+    (rsx_segmented_weighted_histogram), bitwise reproducibly: a tensor [S, B].  keys, offsets, bins, lo, hi, width_shift and descending
+    are segmented_histogram's, and so is the bin of every key.  weights: a tensor shaped like keys.  float32 / float64: every weight
+    is quantised once to an integer mass, floor(|w| * 2^(31 - e)) units with e the smallest exponent such that weight_max <= 2^e
+    (weights beyond it saturate at 2^31 units; NaN weighs nothing), negated for a negative weight — signed=False: negative weights weigh
+    nothing, the mass rule of segmented_weighted_select —, and the masses are added as 64-bit integers, in any order the same.  The result
+    is float64, sum * 2^(e - 31): the sum of the weights as quantised, each within 2^(e - 31) of its value.  weight_max: an upper bound of
+    |weights|; None reads weights.abs().amax() back once, the one host synchronisation of this call.  return_mass=True gives the int64
+    masses themselves.  int32 (non-negative; not checked) / uint32 weights are masses as they stand: exact frequency weights, int64
+    sums, `signed` does not apply.  Bad offsets (all sums are zero then) raise RadixSortError at a later call or synchronisation of the
+    engine."""
+    what = "segmented_weighted_histogram"
+    _whist_weight_type(what, weights)
+    _compact_keys_check(what, keys)
+    if keys.dim() != 1:
+        raise ValueError(f"{what}: keys must be a 1-D device tensor")
+    _args.check_offsets(what, offsets, keys.device, none_ok=True, hint=" (or None: one segment)")
+    nseg = 1 if offsets is None else max(offsets.numel() - 1, 0)
+    return _whist_call(what, keys, offsets, nseg, weights, bins, lo, hi, width_shift, descending, weight_max, signed, return_mass)
+
+
 def _hist_int_check(what: str, x) -> str:
     import torch
     if torch.is_tensor(x) and _args.dtype_name(x) not in _INT_KEY_DTYPES:
@@ -2200,12 +2308,15 @@ def _hist_int_check(what: str, x) -> str:
     return _compact_keys_check(what, x)
 
 
-def bincount(x, minlength: int = 0, num_bins=None):
-    """torch.bincount(x, minlength=minlength) without weights on a 1-D integer device tensor: int64 counts of max(x) + 1 entries, at least
+def bincount(x, minlength: int = 0, num_bins=None, *, weights=None, weight_max=None):
+    """torch.bincount(x, minlength=minlength) on a 1-D integer device tensor: int64 counts of max(x) + 1 entries, at least
     minlength.  The length needs max(x): ONE read-back (Engine.key_range), as torch has one; negative values raise ValueError there.
     num_bins given: exactly max(num_bins, minlength) counters, values from there on and negative ones are dropped, and nothing is read
-    back: no host synchronisation.  Weights are out of scope (a float atomic sum depends on arrival order; see reduce_by_key)."""
+    back: no host synchronisation.  weights (a tensor shaped like x): torch.bincount(x, weights=weights) as a float64 tensor, bitwise
+    reproducible — the signed form of segmented_weighted_histogram, which see for the quantisation and for weight_max (None: one more
+    read-back); int32 / uint32 weights give int64 sums."""
     import torch
+    wkind = None if weights is None else _whist_weight_type("bincount", weights)
     name = _hist_int_check("bincount", x)
     if x.dim() != 1:
         raise ValueError("bincount: x must be a 1-D device tensor")
@@ -2225,23 +2336,36 @@ def bincount(x, minlength: int = 0, num_bins=None):
         nb = max(hi - sign + 1, int(minlength))
         x = k_in
     if nb == 0:
-        return torch.zeros(0, dtype=torch.int64, device=x.device)
+        return torch.zeros(0, dtype=torch.int64 if wkind in (None, WEIGHT_UINT32) else torch.float64, device=x.device)
     if nb > _HIST_MAX_COUNTERS:
         raise ValueError("bincount: at most 2^31 bins (rsx_segmented_histogram's bound)")
+    if weights is not None:
+        return _whist_call("bincount", x, None, 1, weights, nb, 0, None, 0, False, weight_max, True, False).reshape(-1)
     return _hist_call("bincount", x, None, 1, nb, 0, None, 0, False).reshape(-1)
 
 
-def bincount_rows(ids, num_bins: int):
+def bincount_rows(ids, num_bins: int, *, weights=None, weight_max=None):
     """bincount of every row of the integer device tensor `ids` along its last dimension, in ONE rsx_segmented_histogram call: int64
-    counts [..., num_bins]; ids outside [0, num_bins) are dropped.  No host synchronisation.  (torch.bincount is 1-D only.)"""
+    counts [..., num_bins]; ids outside [0, num_bins) are dropped.  No host synchronisation.  (torch.bincount is 1-D only.)  weights (a
+    tensor shaped like ids, e.g. a router's gate values): the weights of every row summed per id in ONE
+    rsx_segmented_weighted_histogram call, float64, bitwise reproducible (the signed form of segmented_weighted_histogram; weight_max
+    None: one read-back; int32 / uint32 weights: int64 sums)."""
     import torch
+    if weights is not None:
+        _whist_weight_type("bincount_rows", weights)
     _hist_int_check("bincount_rows", ids)
     if ids.dim() == 0:
         raise ValueError("bincount_rows: ids must be a device tensor with at least one dimension")
     cols = ids.shape[-1]
     rows = ids.numel() // cols if cols else int(np.prod(ids.shape[:-1], dtype=np.int64))
     offsets = torch.arange(0, rows + 1, device=ids.device, dtype=torch.int64) * cols
-    res = _hist_call("bincount_rows", ids.contiguous().reshape(-1), offsets, rows, int(num_bins), 0, None, 0, False)
+    if weights is not None:
+        if not weights.is_cuda or weights.shape != ids.shape:
+            raise ValueError("bincount_rows: the weights must be a device tensor shaped like ids")
+        res = _whist_call("bincount_rows", ids.contiguous().reshape(-1), offsets, rows, weights.contiguous().reshape(-1), int(num_bins), 0, None, 0, False,
+                          weight_max, True, False)
+    else:
+        res = _hist_call("bincount_rows", ids.contiguous().reshape(-1), offsets, rows, int(num_bins), 0, None, 0, False)
     return res.reshape(tuple(ids.shape[:-1]) + (int(num_bins),))
 
 
@@ -2281,28 +2405,49 @@ def histc(x, bins: int = 100, min=0, max=0):
     return _hist_call("histc", x.contiguous().reshape(-1), None, 1, int(bins), lo, hi, 0, False).reshape(-1).to(x.dtype)
 
 
-def histogram(x, bins, range=None):
-    """torch.histogram(x, bins, range=range) without weights and density on a device tensor: (counts int64, bin_edges).  bins a 1-D tensor
+def _whist_flat(what: str, x, weight):
+    """the weights of a wrapper that flattens x, flattened alike"""
+    if not weight.is_cuda or weight.shape != x.shape:
+        raise ValueError(f"{what}: the weights must be a device tensor shaped like the input")
+    return weight.contiguous().reshape(-1)
+
+
+def histogram(x, bins, range=None, *, weight=None, weight_max=None):
+    """torch.histogram(x, bins, range=range) without density on a device tensor: (counts int64, bin_edges).  bins a 1-D tensor
     of edges of x's dtype (any of the six key dtypes; ascending in this library's order; at most 4096 bins): numpy.histogram(x,
     bins=edges).  bins an int (float dtypes): equal-width bins over range = (lo, hi), or over the data's range (one read-back);
-    bin_edges = torch.linspace(lo, hi, bins + 1); the bin arithmetic is histc's."""
+    bin_edges = torch.linspace(lo, hi, bins + 1); the bin arithmetic is histc's.  weight (a tensor shaped like x): the first result is
+    the sum of the weights per bin, float64 and bitwise reproducible, as numpy.histogram(x, bins, weights=weight) — the signed form of
+    segmented_weighted_histogram, which see for the quantisation and for weight_max (None: one read-back); int32 / uint32 weights give
+    int64 sums."""
     import torch
+    if weight is not None:
+        _whist_weight_type("histogram", weight)
     if torch.is_tensor(bins):
         _compact_keys_check("histogram", x)
         if range is not None:
             raise ValueError("histogram: range belongs to an int bins")
+        if weight is not None:
+            w = _whist_flat("histogram", x, weight)
+            return _whist_call("histogram", x.contiguous().reshape(-1), None, 1, w, bins, None, None, 0, False, weight_max, True, False).reshape(-1), bins
         return _hist_call("histogram", x.contiguous().reshape(-1), None, 1, bins, None, None, 0, False).reshape(-1), bins
     _hist_float_check("histogram", x)
     lo, hi = _hist_float_range("histogram", x, *(range if range is not None else (0, 0)))
-    counts = _hist_call("histogram", x.contiguous().reshape(-1), None, 1, int(bins), lo, hi, 0, False).reshape(-1)
+    if weight is not None:
+        w = _whist_flat("histogram", x, weight)
+        counts = _whist_call("histogram", x.contiguous().reshape(-1), None, 1, w, int(bins), lo, hi, 0, False, weight_max, True, False).reshape(-1)
+    else:
+        counts = _hist_call("histogram", x.contiguous().reshape(-1), None, 1, int(bins), lo, hi, 0, False).reshape(-1)
     return counts, torch.linspace(lo, hi, int(bins) + 1, dtype=x.dtype, device=x.device)
 
 
-def histogram_rows(x, bins, range=None):
+def histogram_rows(x, bins, range=None, *, weight=None, weight_max=None):
     """histogram of every row of the device tensor x along its last dimension, in ONE rsx_segmented_histogram call: (counts int64
     [..., B], bin_edges).  bins and range as histogram; the edges or the range are shared by all rows (an int bins without a range takes
-    the range of the whole tensor)."""
+    the range of the whole tensor).  weight (a tensor shaped like x): the sums of the weights per row and bin, as histogram's."""
     import torch
+    if weight is not None:
+        _whist_weight_type("histogram_rows", weight)
     if x.dim() == 0:
         raise ValueError("histogram_rows: x must be a device tensor with at least one dimension")
     if torch.is_tensor(bins):
@@ -2319,7 +2464,11 @@ def histogram_rows(x, bins, range=None):
     cols = x.shape[-1]
     rows = x.numel() // cols if cols else int(np.prod(x.shape[:-1], dtype=np.int64))
     offsets = torch.arange(0, rows + 1, device=x.device, dtype=torch.int64) * cols
-    res = _hist_call("histogram_rows", x.contiguous().reshape(-1), offsets, rows, bins if torch.is_tensor(bins) else nb, lo, hi, 0, False)
+    if weight is not None:
+        res = _whist_call("histogram_rows", x.contiguous().reshape(-1), offsets, rows, _whist_flat("histogram_rows", x, weight),
+                          bins if torch.is_tensor(bins) else nb, lo, hi, 0, False, weight_max, True, False)
+    else:
+        res = _hist_call("histogram_rows", x.contiguous().reshape(-1), offsets, rows, bins if torch.is_tensor(bins) else nb, lo, hi, 0, False)
     return res.reshape(tuple(x.shape[:-1]) + (nb,)), edges
 
 

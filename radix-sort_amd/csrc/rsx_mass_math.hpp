@@ -1,7 +1,8 @@
 // rsx_mass_math.hpp — the mass of a weight and the target rule of rsx_segmented_weighted_select, pure: a weight is quantised once to a 32-bit
 // fixed-point mass, every sum of masses is a 64-bit integer add, and a target is a mass in [1, total].  No HIP type in here, so that plain
 // g++ compiles it too (host/harness/wselect_selftest.cpp runs it on a case file); under hipcc every function is __host__ __device__.
-// Included by rsx_wselect.hpp.
+// Included by rsx_wselect.hpp, and by rsx_wbins.hpp: rsx_segmented_weighted_histogram sums the same masses per bin, and has a signed form of
+// them (signed_mass_of_bits below; host/harness/whist_selftest.cpp runs it).
 //
 //   mass(w) = 0 unless w > 0 (NaN, negatives and both zeros weigh nothing), else min(floor(w * 2^(31 - weight_exp)), 2^31)
 //
@@ -65,6 +66,30 @@ RSX_MASS_HD uint32_t mass_of_bits(uint64_t bits, uint32_t kind, int32_t weight_e
     if (kind == kWeightUint32) return static_cast<uint32_t>(bits);
     if (kind == kWeightFloat32) return mass_f32_bits(static_cast<uint32_t>(bits), weight_exp);
     return mass_f64_bits(bits, weight_exp);
+}
+
+// The SIGNED mass of a float weight (rsx_segmented_weighted_histogram with RSX_WHIST_SIGNED; float kinds only): the mass of |w| — the
+// sign bit cleared, then the rule above — as `magnitude`, and whether it is added negated.  NaN of either sign and both zeros weigh
+// nothing (and are not negative); -inf weighs -2^31.  The sum a signed mass enters is a two's-complement int64: add
+// signed_addend(magnitude, negative) as a uint64, modulo 2^64.
+struct SignedMass {
+    uint32_t magnitude;
+    bool negative;
+};
+
+RSX_MASS_HD SignedMass signed_mass_of_bits(uint64_t bits, uint32_t kind, int32_t weight_exp)
+{
+    const bool f32 = kind == kWeightFloat32;
+    const uint64_t sign = f32 ? (1ull << 31) : (1ull << 63);
+    const uint64_t low = f32 ? (bits & 0xFFFFFFFFull) : bits;
+    const uint32_t mag = f32 ? mass_f32_bits(static_cast<uint32_t>(low & ~sign), weight_exp) : mass_f64_bits(low & ~sign, weight_exp);
+    return SignedMass{mag, mag != 0u && (low & sign) != 0};
+}
+
+RSX_MASS_HD uint64_t signed_addend(uint32_t magnitude, bool negative)
+{
+    const uint64_t m = magnitude;
+    return negative ? 0ull - m : m;
 }
 
 // The target of one slot as a mass in [1, total]; 0: the slot has no answer.
