@@ -751,6 +751,51 @@ int rsx_segmented_histogram(rsx_engine* e, const void* d_keys, uint64_t n, const
 int rsx_segmented_weighted_histogram(rsx_engine* e, const void* d_keys, const void* d_weights, uint64_t n, const uint64_t* d_offsets /* or NULL */,
                                      uint64_t num_segments, const void* d_edges /* or NULL */, uint64_t lo_bits, uint64_t hi_bits, uint32_t width_shift,
                                      uint64_t num_bins, uint32_t flags, uint32_t weight_kind, int32_t weight_exp, uint64_t* d_sums_out);
+/* rsx_segmented_sample: R categorical draws from every segment, an element drawn with probability proportional to its weight, bitwise
+ *   reproducibly (torch.multinomial with replacement; top-k / top-p / min-p sampling with a bound; ragged rows).  The caller supplies the
+ *   uniforms: there is no random number generator in here.  Nothing is sorted: segment s = [off[s], off[s+1]) has the elements
+ *   i = 0 .. L-1 in INPUT order.
+ *   MASS.  m_i is exactly rsx_segmented_weighted_select's mass of element i's weight: RSX_WEIGHT_UINT32: the stored word, weight_exp must
+ *   be 0; RSX_WEIGHT_FLOAT32 / _FLOAT64: 0 unless w > 0 (NaN, negatives and both zeros weigh nothing), else min(floor(w * 2^(31 -
+ *   weight_exp)), 2^31), |weight_exp| <= 2048.  d_weights == NULL: the keys are their own weights (RSX_KEY_FLOAT engines, weight_kind the
+ *   float kind of the key width).
+ *   BOUND.  With d_bounds (one key per segment) an element the predicate rejects weighs 0.  The predicate is exactly
+ *   rsx_segmented_compact's bound form: key k of segment s is kept iff it does not come after d_bounds[s] in the engine's order (key
+ *   kind, totalOrder, direction), with RSX_COMPACT_STRICT iff it comes strictly before; RSX_COMPACT_INVERT flips it.  Every tie of the
+ *   bound is kept (or, strict, dropped) alike.
+ *   DRAW.  P_i = m_0 + ... + m_i and total = P_(L-1) are 64-bit integer sums.  For every draw q < R with target T the answer is the
+ *   smallest i with P_i >= T: element i answers exactly the targets in (P_(i-1), P_i], so it always has positive mass.
+ *     absolute form: T = ((const uint64_t*)d_targets)[s*R + q]; T == 0 or T > total writes nothing.
+ *     fraction form (RSX_WSELECT_FRACTION): u = ((const double*)d_targets)[s*R + q], T = clamp(ceil((double)total * u), 1, total),
+ *     rsx_segmented_weighted_select's rule unchanged; NaN or total == 0 writes nothing.  For u uniform on [0, 1) element i is drawn with
+ *     probability m_i / total up to the granularity of the doubles.
+ *   WRITTEN.  d_index_out[s*R + q] = i, relative to off[s]; d_mass_out[s*R + q] (or NULL) = P_i; d_total_out[s] (or NULL) = total for
+ *   every segment, empty ones included (0).  A slot without an answer is not written.
+ *   REPRODUCIBLE.  No atomic and no float add decides a result: equal input gives equal bits on every engine, stream, capacity and
+ *   graph replay.
+ *   HOW.  One pass over the 4096-element tiles sums, per tile, the mass of what crosses a tile edge (a tile that holds whole segments
+ *   only is not read); then one wave per (segment, draw) forms the total, the target, walks the segment's tiles 256 at a time to the one
+ *   whose piece holds the crossing, and reads that one piece again.  A segment inside one tile is read by its draws alone.  Bytes: the
+ *   weights (and the keys, with a bound or as weights) once, 16 per tile written, one tile's piece per draw.
+ *   POINTERS AND LIMITS.  Everything is device memory.  d_keys is read only with d_bounds or with d_weights == NULL; otherwise it may be
+ *   NULL.  d_offsets == NULL is the one segment [0, n).  R >= 1, num_segments * R <= 2^31, n <= 2^31, fewer than 2^32 - 1 segments.
+ *   R == 0, n == 0, or no segments with offsets given return RSX_OK and launch nothing.  Keys, when read: 16-byte aligned; weights,
+ *   bounds, targets and outputs: their element size (16-byte aligned weights are read in 16-byte loads).  THE ENGINE'S SORT STATE IS
+ *   UNTOUCHED, whatever the engine's has_payload: n may exceed the capacity and an earlier sort's result stays valid; only the per-tile
+ *   scratch grows (never inside a capture: run one call of the size first).  Asynchronous on the engine's stream, nothing read back,
+ *   capturable.  Offsets are validated on the device: with off[s+1] < off[s] or off[s+1] > n nothing is written and the next rsx_sync /
+ *   rsx_check_status reports RSX_CALCULATION_FAILED once, naming this call and the first such segment; the engine stays usable.
+ *   REFUSED AT ONCE: RSX_CALCULATION_FAILED for a null engine, flag bits other than RSX_WSELECT_FRACTION, RSX_COMPACT_STRICT and
+ *   RSX_COMPACT_INVERT, the last two without d_bounds, a weight_kind above RSX_WEIGHT_FLOAT64, weight_exp != 0 with RSX_WEIGHT_UINT32 or
+ *   beyond +-2048, 2^32 - 1 segments or more, n > 2^31, num_segments * R > 2^31; RSX_HOST_BUFFERS_FAILED for d_weights == NULL on an
+ *   engine whose keys are not floats of weight_kind's width, keys that are read and null or not 16-byte aligned, weights, bounds,
+ *   targets, outputs or offsets not aligned to their element, a null d_targets or d_index_out, an output overlapping an input or another
+ *   output, anything overlapping the engine's buffers. */
+int rsx_segmented_sample(rsx_engine* e, const void* d_keys /* or NULL */, const void* d_weights /* or NULL: the keys are the weights */, uint64_t n,
+                         const uint64_t* d_offsets /* or NULL */, uint64_t num_segments, const void* d_bounds /* or NULL: one key per segment */,
+                         const void* d_targets /* [S*R] uint64 masses, or doubles with RSX_WSELECT_FRACTION */, uint32_t draws_per_segment /* R */,
+                         uint32_t flags, uint32_t weight_kind, int32_t weight_exp, uint32_t* d_index_out, uint64_t* d_mass_out /* or NULL */,
+                         uint64_t* d_total_out /* or NULL */);
 /* rsx_segmented_reduce: SUM, MIN, MAX, ARGMIN or ARGMAX of the values of every segment (cub::DeviceSegmentedReduce; torch.segment_reduce;
  *   x.sum(-1), amax, argmax over the rows of a batch).  Nothing is sorted and there are no keys: the engine's key kind does not matter.
  *   RESULT.  d_values_out[s] = op over v[off[s] .. off[s+1]) for EVERY s < S: dense by segment id, not packed.  d_offsets == NULL is the

@@ -61,7 +61,7 @@ SYMBOLS = [
     "rsx_create", "rsx_destroy", "rsx_set_stream", "rsx_get_stream", "rsx_set_option", "rsx_get_geometry", "rsx_resize",
     "rsx_upload", "rsx_fill_pad", "rsx_download", "rsx_pin_host", "rsx_unpin_host", "rsx_pipeline_submit", "rsx_pipeline_wait", "rsx_host_device_pointer",
     "rsx_histogram", "rsx_scan", "rsx_paste", "rsx_reorder", "rsx_sort", "rsx_sync", "rsx_check_status",
-    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_weighted_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_segmented_merge", "rsx_segmented_set_op", "rsx_segmented_histogram", "rsx_segmented_weighted_histogram", "rsx_segmented_reduce", "rsx_segmented_expand", "rsx_segmented_join", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
+    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_weighted_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_segmented_merge", "rsx_segmented_set_op", "rsx_segmented_histogram", "rsx_segmented_weighted_histogram", "rsx_segmented_sample", "rsx_segmented_reduce", "rsx_segmented_expand", "rsx_segmented_join", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
 ]
 
 
@@ -179,6 +179,7 @@ def load_library() -> C.CDLL:
         "rsx_segmented_set_op": ([P, P, P, U64, P, P, P, U64, P, U64, C.c_uint32, C.c_uint32, P, P, P, P, P], I),
         "rsx_segmented_histogram": ([P, P, U64, P, U64, P, U64, U64, C.c_uint32, U64, C.c_uint32, P], I),
         "rsx_segmented_weighted_histogram": ([P, P, P, U64, P, U64, P, U64, U64, C.c_uint32, U64, C.c_uint32, C.c_uint32, C.c_int32, P], I),
+        "rsx_segmented_sample": ([P, P, P, U64, P, U64, P, P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, P, P, P], I),
         "rsx_segmented_reduce": ([P, P, U64, P, U64, C.c_uint32, C.c_uint32, C.c_uint32, P, P], I),
         "rsx_segmented_expand": ([P, P, U64, C.c_uint32, P, U64, U64, P, C.c_uint32, P, P, P], I),
         "rsx_segmented_join": ([P, P, U64, P, P, U64, P, U64, C.c_uint32, C.c_uint32, U64, P, P, P, P], I),
@@ -688,6 +689,23 @@ class Engine:
             self._h, _opt(d_keys), _opt(d_weights), n, _opt(d_offsets), num_segments, _opt(d_edges), self.key_bits(lo) if even else int(lo),
             self.key_bits(hi) if even else int(hi), width_shift, num_bins, flags, weight_kind, weight_exp, _opt(d_sums_out)),
             "rsx_segmented_weighted_histogram")
+
+    def segmented_sample(self, d_keys: int | None, d_weights: int | None, n: int, d_offsets: int | None, num_segments: int, d_bounds: int | None,
+                         d_targets: int, draws_per_segment: int, flags: int, weight_kind: int, weight_exp: int, d_index_out: int,
+                         d_mass_out: int | None = None, d_total_out: int | None = None) -> None:
+        """draws_per_segment categorical draws from every segment [off[s], off[s+1]), in INPUT order and without sorting: for the target T
+        of slot s * R + q, d_index_out gets the smallest index i (relative to off[s], uint32) whose running mass m_0 + ... + m_i reaches
+        T, d_mass_out (optional) that running mass and d_total_out[s] (optional) the segment's mass.  The mass of a weight is
+        segmented_weighted_select's (weight_kind, weight_exp; d_weights None: the float keys are their own weights).  d_bounds (one key
+        per segment): an element that segmented_compact's bound predicate rejects weighs nothing (flags COMPACT_STRICT, COMPACT_INVERT).
+        d_targets: uint64 masses, or with WSELECT_FRACTION doubles u, T = clamp(ceil(total * u), 1, total).  A slot without an answer
+        (T == 0, T > total, NaN, no mass) is not written.  d_keys is read only with d_bounds or without d_weights.  d_offsets None: ONE
+        segment [0, n).  n may exceed the capacity and the engine's sort result is left alone.  All sums are 64-bit integer adds:
+        bitwise reproducible.  Asynchronous on the engine's stream; bad offsets (nothing is written then) are reported by the next
+        sync() / check_status()."""
+        self._check(self.lib.rsx_segmented_sample(
+            self._h, _opt(d_keys), _opt(d_weights), n, _opt(d_offsets), num_segments, _opt(d_bounds), _opt(d_targets), draws_per_segment, flags,
+            weight_kind, weight_exp, _opt(d_index_out), _opt(d_mass_out), _opt(d_total_out)), "rsx_segmented_sample")
 
     # -- exchange step of the sharded sort on the top B <= 8 bits ----------------
     def msd_count(self, d_keys: int, n: int, bits: int, world: int, d_counts: int) -> None:
@@ -2470,6 +2488,197 @@ def histogram_rows(x, bins, range=None, *, weight=None, weight_max=None):
     else:
         res = _hist_call("histogram_rows", x.contiguous().reshape(-1), offsets, rows, bins if torch.is_tensor(bins) else nb, lo, hi, 0, False)
     return res.reshape(tuple(x.shape[:-1]) + (nb,)), edges
+
+
+# -- categorical draws on torch tensors ---------------------------------------------------------------------------------------------------
+def _sample_weights_check(what: str, weights, word: str = "weights") -> int:
+    """the weight type first (TypeError), then the device (ValueError): the RSX_WEIGHT_* kind"""
+    import torch
+    if not torch.is_tensor(weights):
+        raise TypeError(f"{what}: {word} must be a tensor")
+    kind = _args.weight_kind(what, weights)
+    if not weights.is_cuda:
+        raise ValueError(f"{what}: {word} must be a device tensor (there is no CPU path)")
+    return kind
+
+
+def _sample_targets(what: str, u, targets, nseg: int, device):
+    """Exactly one of u (float64 uniforms; float32 is widened) and targets (int64 / uint64 masses): ([S, R] 8-byte tensor, whether it
+    holds fractions, whether the caller's was 1-D)."""
+    import torch
+    if (u is None) == (targets is None):
+        raise ValueError(f"{what}: give exactly one of u (float64 uniforms in [0, 1)) and targets (int64 masses)")
+    t, word = (targets, "targets") if u is None else (u, "u")
+    if not torch.is_tensor(t) or not t.is_cuda or t.device != device:
+        raise ValueError(f"{what}: {word} must be a device tensor on the weights' device (there is no CPU path)")
+    words = (torch.float32, torch.float64) if u is not None else (torch.int64, getattr(torch, "uint64", torch.int64))
+    if t.dtype not in words:
+        raise TypeError(f"{what}: {word} must be {'float64 (or float32)' if u is not None else 'int64 / uint64 masses'}, not {t.dtype}")
+    if t.dim() not in (1, 2) or t.shape[0] != nseg:
+        raise ValueError(f"{what}: {word} must be shaped [num_segments, R] or [num_segments]")
+    if t.dtype == torch.float32:
+        t = t.to(torch.float64)
+    return t.reshape(nseg, -1).contiguous(), u is not None, t.dim() == 1
+
+
+def segmented_sample(weights, offsets, u=None, targets=None, keys=None, bound=None, strict: bool = False, invert: bool = False,
+                     descending: bool = False, weight_exp: int = 0):
+    """Categorical draws from every segment [offsets[s], offsets[s+1]) of the 1-D device tensor `weights` in ONE engine call
+    (rsx_segmented_sample), bitwise reproducibly and without sorting: element i of a segment, in input order, is drawn with probability
+    mass_i / total.  weights: float32 / float64 (a weight w > 0 weighs min(floor(w * 2^(31 - weight_exp)), 2^31) units, NaN, negatives
+    and zeros nothing) or int32 / uint32 (raw masses; weight_exp must be 0) — segmented_weighted_select's rule.  Exactly one of u
+    (float64 uniforms, float32 is widened: T = clamp(ceil(total * u), 1, total)) and targets (int64 / uint64 masses T) is given, shaped
+    [S, R] or [S]; the answer is the smallest i whose running mass reaches T.  bound (one key per segment): an element that
+    segmented_compact's predicate rejects weighs nothing — a key is kept iff it does not come after the bound (k <= bound ascending,
+    k >= bound with descending=True; strict drops the ties, invert flips; every tie of the bound is treated alike).  The keys the bound
+    is compared with are `keys` (a tensor like weights of a key dtype), or with keys=None the float weights themselves.  Returns
+    (index, mass, total): index int64 [S, R] (or [S] for 1-D u / targets) relative to the segment start, -1 where nothing was drawn
+    (T == 0, T > total, NaN u, a segment without mass); mass int64, the running mass up to and including the answer (0 where nothing was
+    drawn); total int64 [S].  offsets None: one segment.  No host synchronisation; bad offsets raise RadixSortError at a later call or
+    synchronisation of the engine."""
+    import torch
+    what = "segmented_sample"
+    kind = _sample_weights_check(what, weights)
+    if weights.dim() != 1:
+        raise ValueError(f"{what}: weights must be a 1-D device tensor")
+    _args.check_offsets(what, offsets, weights.device, none_ok=True, whose="weights'", hint=" (or None: one segment)")
+    nseg = 1 if offsets is None else max(offsets.numel() - 1, 0)
+    weight_exp = int(weight_exp)
+    if kind == WEIGHT_UINT32 and weight_exp != 0:
+        raise ValueError(f"{what}: integer weights are masses themselves: weight_exp must be 0")
+    if bound is None:
+        if keys is not None:
+            raise ValueError(f"{what}: keys are compared with the bound only: give a bound, or no keys")
+        if strict or invert:
+            raise ValueError(f"{what}: strict and invert belong to the bound")
+        key_name = None
+    else:
+        ktensor = weights if keys is None else keys
+        if keys is None and kind == WEIGHT_UINT32:
+            raise TypeError(f"{what}: without keys the weights are the keys the bound is compared with, which takes float32 or float64 weights, not {weights.dtype}")
+        if keys is not None:
+            if not torch.is_tensor(keys):
+                raise TypeError(f"{what}: keys must be a tensor")
+            _args.key_name(what, keys)
+            if not keys.is_cuda or keys.device != weights.device or keys.shape != weights.shape:
+                raise ValueError(f"{what}: keys must be a device tensor shaped like weights, on the same device")
+        key_name = _args.key_name(what, ktensor)
+        if not torch.is_tensor(bound) or bound.dtype != ktensor.dtype:
+            raise TypeError(f"{what}: the bound must be a tensor of the keys' dtype {ktensor.dtype}")
+        if bound.device != weights.device or bound.numel() != nseg:
+            raise ValueError(f"{what}: the bound must be on the weights' device and hold one key per segment ({nseg})")
+    tt, frac, flat = _sample_targets(what, u, targets, nseg, weights.device)
+    R = tt.shape[1]
+    n = weights.numel()
+    _args.check_count(what, "rsx_segmented_sample", "elements and draws", n, nseg * R)
+    dev = weights.device
+    idx = torch.full((nseg, R), -1, dtype=torch.int32, device=dev)          # the uint32 output's bits: -1 marks an unwritten slot
+    mass = torch.zeros((nseg, R), dtype=torch.int64, device=dev)
+    total = torch.zeros((nseg,), dtype=torch.int64, device=dev)
+    if n > 0 and nseg > 0 and R > 0:
+        ptr = _args.ptr
+        self_weights = bound is not None and keys is None
+        w_in = _aligned_copy(weights) if self_weights else weights.contiguous()
+        k_in = w_in if self_weights else None if keys is None else _aligned_copy(keys)
+        b_in = None if bound is None else bound.contiguous().reshape(-1)
+        off = _args.as_offsets(offsets)
+        flags = (WSELECT_FRACTION if frac else 0) | (COMPACT_STRICT if strict else 0) | (COMPACT_INVERT if invert else 0)
+        eng = _search_engine(*_args.device_and_stream(weights), key_name or "uint32", bool(descending) if key_name else False)
+        eng.segmented_sample(ptr(k_in), None if self_weights else w_in.data_ptr(), n, ptr(off), nseg, ptr(b_in), tt.data_ptr(), R, flags, kind, weight_exp,
+                             idx.data_ptr(), mass.data_ptr(), total.data_ptr())
+        eng.check_status()      # reports bad offsets of calls that have already finished; no synchronisation
+    idx = idx.to(torch.int64)                                                # (positions below 2^31: non-negative as int32)
+    return (idx.reshape(nseg), mass.reshape(nseg), total) if flat else (idx, mass, total)
+
+
+def _sample_uniforms(what: str, u, shape, device, generator):
+    import torch
+    if u is None:
+        return torch.rand(shape, dtype=torch.float64, device=device, generator=generator)
+    if not torch.is_tensor(u) or not u.is_cuda or u.device != device:
+        raise ValueError(f"{what}: u must be a device tensor on probs' device (there is no CPU path)")
+    if u.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{what}: u must be float64 (or float32), not {u.dtype}")
+    if tuple(u.shape) != tuple(shape):
+        raise ValueError(f"{what}: u must be shaped {tuple(shape)}: one uniform per draw")
+    return u
+
+
+def multinomial(probs, num_samples: int, dim: int = -1, u=None, generator=None, weight_max=None):
+    """torch.multinomial(probs, num_samples, replacement=True) on a device tensor, for the rows along `dim` in ONE rsx_segmented_sample
+    call: int64 [..., num_samples], the drawn positions along `dim`.  The draws are WITH replacement (replacement=False is not offered).
+    u: the uniforms in [0, 1), float64 shaped like the result; None draws them with torch.rand(..., dtype=float64, generator=generator).
+    Given u the result is a pure function of (probs, u): equal bits on every run, stream and engine, which torch's float prefix sums do
+    not promise.  Weights are quantised once to integer masses: a weight w weighs floor(w * 2^(31 - e)) units with e the smallest
+    exponent such that weight_max <= 2^e.  weight_max=None assumes PROBABILITIES (e = 0): weights above 1 then saturate at 2^31 units
+    and are drawn as if they were 1 — pass an upper bound of the weights for unnormalised ones; nothing is read back to find one.
+    Weights below 2^(e - 31) weigh nothing.  A row without mass gives -1 where torch raises.  dtypes: float32, float64 (int32 / uint32
+    are masses as they stand).  No host synchronisation."""
+    import torch
+    what = "multinomial"
+    kind = _sample_weights_check(what, probs, "probs")
+    num_samples = int(num_samples)
+    if num_samples < 1:
+        raise ValueError(f"{what}: num_samples must be at least 1")
+    if probs.dim() == 0:
+        raise ValueError(f"{what}: probs must have at least one dimension")
+    dim = dim % probs.dim()
+    pm = probs.movedim(dim, -1)
+    lead, size = tuple(pm.shape[:-1]), pm.shape[-1]
+    rows = int(np.prod(lead, dtype=np.int64))
+    uu = _sample_uniforms(what, u, lead + (num_samples,), probs.device, generator)
+    if rows == 0 or size == 0:
+        return torch.full(lead + (num_samples,), -1, dtype=torch.int64, device=probs.device)
+    wexp = 0 if weight_max is None or kind == WEIGHT_UINT32 else _weight_exp_of(float(weight_max))
+    offsets = torch.arange(0, rows + 1, device=probs.device, dtype=torch.int64) * size
+    idx, _, _ = segmented_sample(pm.contiguous().reshape(-1), offsets, u=uu.reshape(rows, num_samples), weight_exp=wexp)
+    return idx.reshape(lead + (num_samples,))
+
+
+def sample_rows(probs, u=None, top_k=None, top_p=None, min_p=None, generator=None):
+    """One token per row of the float32 / float64 device tensor `probs` (rows along the last dimension), drawn with probability
+    proportional to its entry among the entries that pass the filters given: int64, probs' shape without its last dimension.
+    Every threshold is taken from the UNFILTERED row by the existing calls — top_p: the nucleus threshold of top_p(probs, top_p); top_k:
+    the k-th largest value (kthvalue); min_p: min_p * amax(row) — and the row's bound is the largest of those given.  Then ONE
+    rsx_segmented_sample call draws among the entries >= bound, the probabilities being their own weights (weight_exp = 0: an entry
+    weighs floor(p * 2^31) units).  Nothing is written out, sorted or read back: no host synchronisation.  u: float64 uniforms, one per
+    row; None draws them with torch.rand(..., dtype=float64, generator=generator).  Given u the result is bitwise reproducible.
+    Two differences from sequential filtering with renormalisation (the order of Hugging Face's logits warpers: top-k, then top-p of the
+    renormalised survivors, then min-p): (1) each filter sees the whole row, so top_p=0.9 after top_k keeps the nucleus of the ORIGINAL
+    distribution cut at the k-th value — the intersection of the filters — where the sequential order keeps 90 % of the top-k mass;
+    (2) every entry that ties with the bound is kept, as compact_rows does, so more than k entries pass top_k when the k-th value
+    repeats.  Renormalisation itself is implied: the draw is proportional among the survivors.  A row without mass gives -1."""
+    import torch
+    what = "sample_rows"
+    if torch.is_tensor(probs) and _args.weight_kind(what, probs) == WEIGHT_UINT32:
+        raise TypeError(f"{what}: unsupported dtype {probs.dtype} (float32 and float64)")
+    _sample_weights_check(what, probs, "probs")
+    if probs.dim() == 0:
+        raise ValueError(f"{what}: probs must have at least one dimension")
+    lead, size = tuple(probs.shape[:-1]), probs.shape[-1]
+    rows = int(np.prod(lead, dtype=np.int64))
+    uu = _sample_uniforms(what, u, lead, probs.device, generator)
+    if rows == 0 or size == 0:
+        return torch.full(lead, -1, dtype=torch.int64, device=probs.device)
+    bound = None
+    if top_p is not None:
+        bound = globals()["top_p"](probs, top_p, dim=-1)[0]
+    if top_k is not None:
+        k = int(top_k)
+        if k < 1:
+            raise ValueError(f"{what}: top_k must be at least 1")
+        kth = kthvalue(probs, size - min(k, size) + 1, dim=-1)[0]
+        bound = kth if bound is None else torch.maximum(bound, kth)
+    if min_p is not None:
+        floor = amax(probs, dim=-1) * min_p
+        bound = floor if bound is None else torch.maximum(bound, floor)
+    offsets = torch.arange(0, rows + 1, device=probs.device, dtype=torch.int64) * size
+    flat = probs.contiguous().reshape(-1)
+    if bound is None:
+        idx, _, _ = segmented_sample(flat, offsets, u=uu.reshape(rows))
+    else:
+        idx, _, _ = segmented_sample(flat, offsets, u=uu.reshape(rows), bound=bound.to(probs.dtype).reshape(rows), descending=True)
+    return idx.reshape(lead)
 
 
 # -- merge on torch tensors -------------------------------------------------------------------------------------------------------------

@@ -27,6 +27,7 @@
 #include "rsx_join.hpp"
 #include "rsx_bins.hpp"
 #include "rsx_wbins.hpp"
+#include "rsx_sample.hpp"
 #include "rsx_args.hpp"
 
 #include <hip/hip_runtime.h>
@@ -1288,6 +1289,7 @@ constexpr uint32_t kStatusCallExpand = 5;
 constexpr uint32_t kStatusCallJoin = 6;
 constexpr uint32_t kStatusCallWselect = 7;
 constexpr uint32_t kStatusCallWhistogram = 8;
+constexpr uint32_t kStatusCallSample = 9;
 int check_scan_timeout(rsx_engine* e, int status)
 {
     if (e->seg_status_host) {
@@ -1324,6 +1326,9 @@ int check_scan_timeout(rsx_engine* e, int status)
                 return fail(status, ("rsx_segmented_weighted_select: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; it was neither "
                                      "read nor written, d_total_out[s] included (the first such segment of the call; reported once; the engine remains "
                                      "usable)").c_str());
+            if (call == kStatusCallSample)
+                return fail(status, ("rsx_segmented_sample: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; nothing was written (the "
+                                     "first such segment of the call; reported once; the engine remains usable)").c_str());
             if (call == kStatusCallWhistogram)
                 return fail(status, ("rsx_segmented_weighted_histogram: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; every sum of "
                                      "d_sums_out is zero (the first such segment of the call; reported once; the engine remains usable)").c_str());
@@ -2461,6 +2466,7 @@ int rsx_peer_enable(rsx_engine* e, int peer_device)
 #include "capi_setop.inc"
 #include "capi_histogram.inc"
 #include "capi_whistogram.inc"
+#include "capi_sample.inc"
 #include "capi_segreduce.inc"
 #include "capi_expand.inc"
 #include "capi_join.inc"
