@@ -10,6 +10,12 @@ sample_loop    the definition, element by element with Python integers, for the 
 For the path tests (tests/test_sample.py checks on the CPU that each layout reaches the path it is named for):
 walk_facts     what sample_draw_kernel's walk meets on one segment: its tiles, the chunks of WALK_TILES, the prefix at every chunk's end.
 tile_sums      which tiles sample_tile_kernel reads: 'both' (inside one long segment), 'lead', 'tail', 'lead+tail', or None (not read).
+tile_grid      (chunk, grid) of sample_tile_kernel's launch; group_walk: the tile_sums kinds of every workgroup's tiles, 'outside' for a
+               tile the workgroup skips because it lies outside [off[0], off[S]).
+group_edges    the 256-element group boundaries of every piece of a segment with the running mass there; group_targets: those and + 1.
+
+The layouts of tests/test_gpu_sample_paths.py (two_tile_layout, group_layout, second_trip_layout, huge_total_layout) take the CU count
+where the path depends on it.
 """
 import numpy as np
 
@@ -195,3 +201,154 @@ LAYOUTS = {
     "one_tile": one_tile_layout, "crossing": crossing_layout, "hollow": hollow_layout, "long": long_layout, "many": many_layout,
     "inner": inner_layout,
 }
+
+
+# -- the launch paths that need the CU count (tests/test_gpu_sample_paths.py) -------------------------------------------------------------------------
+
+def tile_grid(n, cus=256):
+    """(chunk, grid) of sample_tile_kernel: capi_family.inc's tile_chunks"""
+    ntiles = (n + TILE - 1) // TILE
+    chunk = (ntiles + cus * 16 - 1) // (cus * 16)
+    return chunk, (ntiles + chunk - 1) // chunk
+
+
+def group_walk(n, off, cus=256):
+    """per workgroup of sample_tile_kernel the kinds of its tiles in the order it walks them: tile_sums' kinds, with 'outside' for a
+    tile that ends at or before off[0] or begins at or behind off[S] (the `continue` of the tile loop)"""
+    o = C._offsets(n, off)
+    lo, hi = int(o[0]), int(o[-1])
+    kinds = tile_sums(n, off)
+    for t in range(len(kinds)):
+        if t * TILE >= hi or (t + 1) * TILE <= lo:
+            kinds[t] = "outside"
+    chunk, grid = tile_grid(n, cus)
+    return [tuple(kinds[g * chunk:(g + 1) * chunk]) for g in range(grid)]
+
+
+SHORT_TILES = 4                                   # tiles 8 .. 11 of two_tile_layout hold whole short segments only
+SHORT_PER_TILE = TILE // 7                        # 585 segments of 7 elements and one of 1 fill a tile exactly
+
+
+def two_tile_layout(cus=256):
+    """(n, off, names): n = (16 cus + 3) tiles + 77, so a workgroup of sample_tile_kernel walks two tiles: tiles 2g and 2g + 1.
+    names: the segment index of 'few', 'two_edges', 'to_edge' (ends on the edge 5 T behind three empty segments, two more empty ones
+    on that edge), 'from_edge' (three tiles, from that edge), 'short' (the first of the short ones), 'bulk', 'last'.
+
+    tile 0 outside, tile 1 tail (off[0] in the middle of a workgroup's SECOND tile); 2 both, 3 lead+tail (again a second tile), 4 lead,
+    5 tail, 6 both, 7 lead; 8 .. 11 not read: 4 x (585 segments of 7 and one of 1); 12 tail, 13 lead+tail: the bulk begins in tile 13
+    (13 % 4 = 1) and ends in tile 16 cus + 2, the FIRST tile of the last workgroup, whose second tile lies behind off[S]."""
+    T = TILE
+    n = (16 * cus + 3) * T + 77
+    last_tile = 16 * cus + 2
+    lengths, names = [], {}
+
+    def add(name, *ls):
+        names[name] = len(lengths)
+        lengths.extend(ls)
+
+    start = T + 2000
+    add("few", 300)
+    add("two_edges", 3 * T + 500 - (start + 300))          # over the edges 2 T and 3 T
+    add("empty", 0, 0, 0)
+    add("to_edge", 5 * T - (3 * T + 500))                  # over the edge 4 T, ends on 5 T
+    add("empty_on_edge", 0, 0)
+    add("from_edge", 3 * T)                                # tiles 5, 6, 7
+    add("short", *(([7] * SHORT_PER_TILE + [T - 7 * SHORT_PER_TILE]) * SHORT_TILES))
+    add("before_bulk", T + 1500)                           # from 12 T into tile 13
+    bulk_start = 13 * T + 1500
+    add("bulk", last_tile * T + 1000 - bulk_start)
+    add("last", 50)
+    off = C.offsets_from(lengths, start=start)
+    assert int(off[names["bulk"]]) == bulk_start and int(off[-1]) == last_tile * T + 1050 < n
+    return n, off, names
+
+
+def weightless_chunk(off, s):
+    """[a, b): the elements of segment s in the 256 tiles from its first tile + 256 on, the walk's second chunk; the tests zero them"""
+    a, b = int(off[s]), int(off[s + 1])
+    ta = a // TILE
+    return min((ta + WALK_TILES) * TILE, b), min((ta + 2 * WALK_TILES) * TILE, b)
+
+
+def chunk_targets(m, off, s, chunks=8):
+    """1, total, and the prefix and prefix + 1 of the first `chunks` chunk ends of segment s"""
+    f = walk_facts(m, off, s)
+    t = [1, sum(f["pieces"])]
+    for p in f["chunk_prefix"][:chunks]:
+        t += [p, p + 1]
+    return t
+
+
+GROUP_ONE_TILE, GROUP_TWO_TILES = 1, 0            # segments of group_layout
+
+
+def group_layout():
+    """(n, off): segment 0 = [501, T + 1001): pieces of 3595 and 1001 elements, both partial, the first one off the 4-element grid;
+    segment 1 = [T + 1001, T + 4001): inside tile 1, off the grid, 11 whole groups of 256 and one of 184"""
+    off = np.array([501, TILE + 1001, TILE + 4001], dtype=np.uint64)
+    return 2 * TILE + 1000, off
+
+
+def group_edges(m, off, s):
+    """[(edge, prefix)]: for every piece of segment s and every end of a 256-element group of it (the piece's end included), the index
+    in the segment and the segment's running mass in front of it"""
+    o = np.asarray(off).astype(np.int64)
+    a, b = int(o[s]), int(o[s + 1])
+    run = np.concatenate([[0], np.cumsum(np.asarray(m, dtype=np.int64))])
+    out = []
+    for t in range(a // TILE, (b - 1) // TILE + 1 if b > a else 0):
+        ps, pe = max(a, t * TILE), min(b, (t + 1) * TILE)
+        for e in list(range(ps + GROUP, pe, GROUP)) + [pe]:
+            out.append((e - a, int(run[e] - run[a])))
+    return out
+
+
+def group_targets(m, off, s):
+    """the running mass at every group boundary of segment s and that plus 1, without 0, repeats and what lies above the total"""
+    edges = group_edges(m, off, s)
+    total = edges[-1][1] if edges else 0
+    out = []
+    for _, p in edges:
+        for t in (p, p + 1):
+            if 1 <= t <= total and t not in out:
+                out.append(t)
+    return out
+
+
+SECOND_TRIP_R = 3
+
+
+def second_trip_layout(cus=256, seed=6):
+    """(n, off, names): 48 cus segments of 0 .. 7 elements drawn 3 times each: 144 cus slots on a draw grid of 32 cus workgroups of 4
+    waves, so the slots from 128 cus on belong to the second trip.  Among the last 5 cus segments (first slot >= 129 cus): 'two_tiles',
+    'long' (300 tiles: two walk chunks), 'empty' and 'one_tile' (3000 elements inside one tile)"""
+    rng = np.random.default_rng(seed)
+    nseg = 48 * cus
+    lengths = rng.integers(0, 8, nseg)
+    first = nseg - 5 * cus
+    names = {"two_tiles": first + cus, "long": first + 2 * cus, "empty": first + 3 * cus, "one_tile": first + 4 * cus}
+    lengths[names["two_tiles"]] = TILE + 700
+    lengths[names["long"]] = 299 * TILE + 9
+    lengths[names["empty"]] = 0
+    lengths[names["one_tile"]] = 3000
+    off = C.offsets_from(lengths, start=5)
+    # the pieces as named: move the starts where the random lengths before them put them badly
+    for name, want_tiles in (("two_tiles", 2), ("long", 300), ("one_tile", 1)):
+        s = names[name]
+        a, b = int(off[s]), int(off[s + 1])
+        pad = 0
+        while (b + pad - 1) // TILE - (a + pad) // TILE + 1 != want_tiles:
+            pad += 512
+        if pad:
+            lengths[s - 1] += pad
+            off = C.offsets_from(lengths, start=5)
+    return int(off[-1]) + 3, off, names
+
+
+HUGE_LENGTH = (1 << 22) + 3 * TILE + 5
+
+
+def huge_total_layout():
+    """(n, off): one segment of 2^22 + 3 tiles + 5 elements from element 7 on (1028 tiles: five walk chunks), 9 elements behind it"""
+    off = np.array([7, 7 + HUGE_LENGTH], dtype=np.uint64)
+    return 7 + HUGE_LENGTH + 9, off

@@ -9,8 +9,9 @@ _histogram_ref.bins_of, and — from the layout alone — the path every piece o
   piece_paths         _histogram_ref.piece_paths with THIS kernel's constants: 2048 bins in LDS, wave-private up to 512, direct pieces below
                       256 keys (_histogram_ref reads its module constants, which are the unweighted kernel's)
   lds_layout          'wave_private' / 'shared' / 'none' for B bins
+  big_boundaries_layout  the two-tile layout of tests/test_gpu_whistogram_paths.py for a CU count
   case_weights        the float weights of the GPU tests: negatives, +-0, NaNs, +-inf and one weight at or above 2^weight_exp planted
-                      inside the segments; uint32_weights the integer ones
+                      inside the segments; uint32_weights the integer ones; large_case_weights the same for the largest uploads
 The sums are compared as int64 words: an unsigned sum below 2^63 reads the same either way.
 """
 import numpy as np
@@ -142,6 +143,14 @@ def piece_slots(n, off, B, cus=256):
     return out
 
 
+def big_boundaries_layout(cus=256):
+    """(n, off): _histogram_ref.big_boundaries_layout for any CU count: n = (16 cus + 1) tiles + 5, so a workgroup of wbins_tile_kernel
+    walks two tiles, with the same offsets relative to the tiles: off[0] and off[S] in mid-tile, a boundary in the middle of a
+    workgroup's SECOND tile (tile 3: both pieces long), of its first tile (tile 8), and a short piece at a tile's end (tile 13)"""
+    n = (16 * cus + 1) * TILE + 5
+    return n, np.array([1000, 3 * TILE + 2000, 8 * TILE + 300, 13 * TILE + 4000, 14 * TILE + 50, n - 3], dtype=np.uint64)
+
+
 def lds_layout(B):
     """'wave_private' or 'shared' or 'none': the counters of the LDS path for B bins"""
     return "none" if B > LDS_MAX else "wave_private" if B <= WAVE_PRIVATE_MAX else "shared"
@@ -183,6 +192,20 @@ def case_weights(rng, wdt, n, off, weight_exp=0):
     w = ((rng.random(n) * 2.0 - 1.0) * np.ldexp(1.0, weight_exp)).astype(wdt)
     w[rng.random(n) < 0.1] = 0.0
     return H.scatter_into(rng, w, off, specials(wdt, weight_exp))
+
+
+def large_case_weights(rng, wdt, n, off, weight_exp=0):
+    """case_weights for the uploads of 2^24 elements and more: the same values, the float specials at random positions of
+    [off[0], off[S]) that may coincide (scatter_into permutes the whole range to keep them apart)"""
+    wdt = np.dtype(wdt)
+    if wdt == np.uint32:
+        return case_weights(rng, wdt, n, off)
+    w = ((rng.random(n) * 2.0 - 1.0) * np.ldexp(1.0, weight_exp)).astype(wdt)
+    w[rng.random(n, dtype=np.float32) < 0.1] = 0.0
+    o = H._offsets(n, off)
+    sp = np.tile(specials(wdt, weight_exp), 4)
+    w[rng.integers(int(o[0]), int(o[-1]), sp.size)] = sp
+    return w
 
 
 def dyadic_weights(rng, n, dtype=np.float32):

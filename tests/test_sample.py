@@ -239,6 +239,118 @@ def test_layouts_reach_their_paths():
     assert kinds == {(True, 0), (True, 1), (False, 1)} and "both" in R.tile_sums(n, off)
 
 
+# -- the launch paths of tests/test_gpu_sample_paths.py, from the layouts alone, at 256 CUs and at one other count ----------------------------------
+
+def _not_read_run(walk):
+    """the longest run of consecutive tiles that sample_tile_kernel does not read, over the workgroups in order"""
+    best = run = 0
+    for kind in (k for g in walk for k in g):
+        run = run + 1 if kind is None else 0
+        best = max(best, run)
+    return best
+
+
+@pytest.mark.parametrize("cus", [256, 304, 128])
+def test_two_tile_layout_reaches_its_paths(cus):
+    n, off, names = R.two_tile_layout(cus)
+    o = off.astype(np.int64)
+    assert n == (16 * cus + 3) * R.TILE + 77 and R.tile_grid(n, cus) == (2, 8 * cus + 2)
+    walk = R.group_walk(n, off, cus)
+    assert len(walk) == 8 * cus + 2 and all(len(g) == 2 for g in walk)
+    assert walk[0] == ("outside", "tail")                                          # off[0] in a workgroup's second tile
+    assert walk[1] == ("both", "lead+tail")                                        # two block sums behind a tile already summed
+    assert walk[-1] == ("lead", "outside") and o[-1] % R.TILE and o[-1] < n        # off[S] in a workgroup's first tile
+    assert _not_read_run(walk) >= 3 and walk[4] == walk[5] == (None, None)
+    lens = np.diff(o)
+    first = names["short"]
+    assert int((lens[first:names["before_bulk"]] == 7).sum()) >= 1800 and o[first] == 8 * R.TILE and o[names["before_bulk"]] == 12 * R.TILE
+    # a segment ends and another begins on one tile edge, with empty segments before and on it
+    e, b = names["to_edge"], names["from_edge"]
+    assert o[e + 1] == o[b] == 5 * R.TILE and b == e + 3 and not lens[e + 1:b].any() and not lens[names["empty"]:e].any() and e == names["empty"] + 3
+    assert (o[b + 1] - o[b]) == 3 * R.TILE and o[e] // R.TILE == 3
+    ones = np.ones(n, dtype=np.int64)
+    assert R.walk_facts(ones, off, names["two_edges"])["tiles"] == (1, 3) and R.walk_facts(ones, off, names["few"])["one_tile"]
+    # the bulk: at least 3 walk chunks (16 at 256 CUs), from a tile that is no multiple of 4 to the first tile of a workgroup
+    s = names["bulk"]
+    a, z = R.weightless_chunk(off, s)
+    m = ones.copy()
+    m[a:z] = 0
+    f = R.walk_facts(m, off, s)
+    ta, tb = f["tiles"]
+    assert f["chunks"] >= (16 if cus >= 256 else 3) and ta % 4 != 0 and tb % 2 == 0 and tb == 16 * cus + 2
+    assert (a, z) == ((ta + R.WALK_TILES) * R.TILE, (ta + 2 * R.WALK_TILES) * R.TILE) and z < o[s + 1]
+    assert f["chunk_prefix"][1] == f["chunk_prefix"][0] > 0 and f["chunk_prefix"][2] > f["chunk_prefix"][1]      # the weightless chunk
+    assert not any(f["pieces"][R.WALK_TILES:2 * R.WALK_TILES]) and all(f["pieces"][:R.WALK_TILES])
+    t = R.chunk_targets(m, off, s)
+    assert len(t) == 2 + 2 * min(8, f["chunks"] - 1) <= 32
+
+
+@pytest.mark.parametrize("cus", [256, 304, 128])
+def test_second_trip_layout_reaches_its_path(cus):
+    n, off, names = R.second_trip_layout(cus)
+    nseg = len(off) - 1
+    grid, slots = R.draw_grid(nseg, R.SECOND_TRIP_R, cus)
+    assert nseg == 48 * cus and grid == 32 * cus and slots == 144 * cus > R.WAVES * grid
+    assert all(s * R.SECOND_TRIP_R >= R.WAVES * grid and s >= nseg - 5 * cus for s in names.values())           # every planted slot in the second trip
+    ones = np.ones(n, dtype=np.int64)
+    facts = {name: R.walk_facts(ones, off, s) for name, s in names.items()}
+    assert facts["two_tiles"]["chunks"] == 1 and len(facts["two_tiles"]["pieces"]) == 2
+    assert facts["long"]["chunks"] == 2 and len(facts["long"]["pieces"]) == 300
+    assert facts["empty"]["tiles"] is None and facts["one_tile"]["one_tile"] and int(off[names["one_tile"] + 1] - off[names["one_tile"]]) == 3000
+    a, z = R.weightless_chunk(off, names["long"])
+    m = ones.copy()
+    m[a:z] = 0
+    f = R.walk_facts(m, off, names["long"])
+    assert z == int(off[names["long"] + 1]) and sum(f["pieces"][R.WALK_TILES:]) == 0 and f["chunk_prefix"][0] == sum(f["pieces"]) > 0
+    lens = np.diff(off.astype(np.int64))
+    small = np.delete(lens, [s for s in names.values()] + [s - 1 for s in names.values()])
+    assert set(small.tolist()) == set(range(8))
+
+
+def test_group_layout_and_targets():
+    n, off = R.group_layout()
+    ones = np.ones(n, dtype=np.int64)
+    f = R.walk_facts(ones, off, R.GROUP_ONE_TILE)
+    a = int(off[R.GROUP_ONE_TILE])
+    assert f["one_tile"] and a == R.TILE + 1001 and a % 4 and f["pieces"] == [3000] and divmod(3000, R.GROUP) == (11, 184)
+    f = R.walk_facts(ones, off, R.GROUP_TWO_TILES)
+    assert f["pieces"] == [3595, 1001] and int(off[0]) % 4 and all(p % R.GROUP for p in f["pieces"])
+    assert [e for e, _ in R.group_edges(ones, off, R.GROUP_ONE_TILE)] == list(range(256, 3000, 256)) + [3000]
+    assert [e for e, _ in R.group_edges(ones, off, R.GROUP_TWO_TILES)] == list(range(256, 3595, 256)) + [3595] + list(range(3595 + 256, 4596, 256)) + [4596]
+    # a group of zero mass: its end's prefix repeats and is dropped; nothing is 0 or above the total
+    m = ones.copy()
+    m[a + 3 * R.GROUP:a + 4 * R.GROUP] = 0
+    t = R.group_targets(m, off, R.GROUP_ONE_TILE)
+    assert t == sorted(set(t)) and t[0] == 256 and t[-1] == 3000 - 256 and 768 in t and 769 in t and len(t) == 2 * 11 - 1
+    assert len(R.group_targets(ones, off, R.GROUP_TWO_TILES)) == 2 * 19 - 1
+
+
+def test_huge_total_layout_passes_2_to_53_in_both_directions():
+    n, off = R.huge_total_layout()
+    length = int(off[1] - off[0])
+    assert length == (1 << 22) + 3 * R.TILE + 5 and int(off[0]) > 0 and n > int(off[1])
+    f = R.walk_facts(np.ones(n, dtype=np.int64), off, 0)
+    assert len(f["pieces"]) == 1028 and f["chunks"] == 5
+    up, down = length * 0xFFFFFFFF, length * 0xFFFFFFFD
+    assert up > down > 1 << 53
+    assert int(float(up)) - up == 1 and int(float(down)) - down == -1              # the double nearest the total lies above it, and below it
+    w = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
+    assert int(R.Referee(w, off).total[0]) == up and int(R.Referee(w - np.uint32(2), off).total[0]) == down
+
+
+def test_first_suite_stays_on_one_tile_per_workgroup():
+    """the gap that tests/test_gpu_sample_paths.py closes: no layout of tests/test_gpu_sample.py gives a workgroup of sample_tile_kernel a
+    second tile at any CU count from 64 on, or a walk a third chunk"""
+    layouts = [f() for f in R.LAYOUTS.values()] + [_compact_ref.ragged_layout(), (3 * 4096 + 17, np.array([7, 5000, 5000, 3 * 4096 + 7], dtype=np.uint64))]
+    for n, off in layouts:
+        assert R.tile_grid(n, 64)[0] == R.tile_grid(n, 256)[0] == 1
+        ones = np.ones(n, dtype=np.int64)
+        long_ones = np.flatnonzero(np.diff(off.astype(np.int64)) > R.TILE)
+        assert all(R.walk_facts(ones, off, s)["chunks"] <= 2 for s in long_ones)
+    n, off = R.many_layout()
+    assert R.draw_grid(len(off) - 1, 1)[1] > R.WAVES * R.draw_grid(len(off) - 1, 1)[0] and np.diff(off.astype(np.int64)).max() <= 7     # the one second trip: R = 1, short segments
+
+
 # -- no CPU path ---------------------------------------------------------------------------------------------------------------------------------
 
 def test_no_cpu_path(rsx):

@@ -196,6 +196,35 @@ def test_slot_layouts_fill_their_slots():
     assert paths == {"lds_first", "lds_same", "lds_flush", "direct"}
 
 
+@pytest.mark.parametrize("cus", [256, 128, 304])
+def test_two_tile_layout_reaches_carry_and_flush_with_shared_counters(cus):
+    """the layout of tests/test_gpu_whistogram_paths.py: two tiles per workgroup at any CU count, every LDS path with one shared counter
+    copy (513 and 2048 bins) and with the last wave-private size, and nothing but direct adds from 2049 bins on"""
+    n, off = W.big_boundaries_layout(cus)
+    assert n == (16 * cus + 1) * H.TILE + 5 and H.chunk_of(n, cus) == 2 and H.chunk_of(16 * cus * H.TILE, cus) == 1
+    assert (n, off.tolist()) == (H.big_boundaries_layout()[0], H.big_boundaries_layout()[1].tolist()) or cus != 256
+    for B, layout in ((512, "wave_private"), (513, "shared"), (2048, "shared")):
+        paths = W.piece_paths(n, off, B, cus)
+        assert W.lds_layout(B) == layout and {p[3] for p in paths} == {"lds_first", "lds_same", "lds_flush", "direct"}
+        by_tile = {}
+        for t, s, length, path in paths:
+            by_tile.setdefault(t, []).append((s, path))
+        assert by_tile[2] == [(0, "lds_first")] and by_tile[3] == [(0, "lds_same"), (1, "lds_flush")]         # carried into a second tile, flushed inside it
+        assert by_tile[8] == [(1, "lds_first"), (2, "lds_flush")] and by_tile[9] == [(2, "lds_same")]         # flushed in a first tile, carried on
+        assert by_tile[13] == [(2, "lds_same"), (3, "direct")]
+    assert {p[3] for p in W.piece_paths(n, off, 2049, cus)} == {"direct"}
+
+
+def test_first_suite_has_one_two_tile_case():
+    """the gap that tests/test_gpu_whistogram_paths.py closes: test_carry_over_and_flush is the only case of tests/test_gpu_whistogram.py
+    whose workgroups walk two tiles, and it has wave-private counters"""
+    two_tile = [name for name, (layout, B, _) in W.LAYOUTS.items() if H.chunk_of(layout()[0]) > 1]
+    assert two_tile == ["big_boundaries"] and W.LAYOUTS["big_boundaries"][1] == 256 and W.lds_layout(256) == "wave_private"
+    assert H.chunk_of(H.SKEW_N) == 1 and H.chunk_of(1 << 16) == 1 and all(H.chunk_of(f()[0]) == 1 for f in H.SLOT_LAYOUTS.values())
+    text = open(os.path.join(ROOT, "tests", "test_gpu_whistogram.py")).read()
+    assert text.count("big_boundaries_layout") == 1 and text.count("BIG_N") == 0
+
+
 # -- the torch helpers refuse host tensors and foreign weight dtypes ---------------------------------------------------------------------------------
 
 def test_no_cpu_path(rsx):
