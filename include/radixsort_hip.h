@@ -796,6 +796,42 @@ int rsx_segmented_sample(rsx_engine* e, const void* d_keys /* or NULL */, const 
                          const void* d_targets /* [S*R] uint64 masses, or doubles with RSX_WSELECT_FRACTION */, uint32_t draws_per_segment /* R */,
                          uint32_t flags, uint32_t weight_kind, int32_t weight_exp, uint32_t* d_index_out, uint64_t* d_mass_out /* or NULL */,
                          uint64_t* d_total_out /* or NULL */);
+/* rsx_segmented_rank: the rank of every key inside its segment, under one of five tie rules, and the size of its tie group
+ *   (scipy.stats.rankdata; pandas / cuDF groupby().rank(method=); argsort(argsort(x)) with ties settled).
+ *   RESULT.  For every i in [off[s], off[s+1]): d_rank_out[i] is the 0-based rank of d_keys[i] inside segment s in the ENGINE'S ORDER: its
+ *   ascending / descending setting and key codec over all six key kinds, floats in IEEE 754 totalOrder (-0.0 before +0.0, NaNs ordered
+ *   by sign and payload), equality by bit pattern, exactly as rsx_segmented_unique groups.  d_ties_out[i] (or NULL: skipped) is the
+ *   number of keys of segment s with d_keys[i]'s bits.  With run = the keys equal to d_keys[i], before = the keys strictly before them:
+ *     RSX_RANK_ORDINAL  the position in the segment's stable sort (ties in index order): rsx_segmented_sort's iota payload, inverted
+ *     RSX_RANK_MIN      |before|                       RSX_RANK_MAX      |before| + |run| - 1
+ *     RSX_RANK_DENSE    the DISTINCT keys in before     RSX_RANK_AVERAGE  MIN + MAX: twice the average rank, an exact integer
+ *   Equal keys on the two sides of a segment boundary are two groups.  Positions outside [off[0], off[S]) are not written; empty
+ *   segments write nothing.  d_offsets == NULL is the one segment [0, n).
+ *   REPRODUCIBLE.  No atomic and no float operation decides a result: equal input gives equal bits on every engine, stream, capacity
+ *   and graph replay.
+ *   HOW.  Segments of 2..4096 keys: one workgroup each sorts (encoded key, position) inside LDS in the segmented sort's three class
+ *   shapes, flags the heads of the runs, scans them three ways (run start, run end, distinct before) and stores the ranks in index order:
+ *   n*K bytes read, n*4 (n*8 with ties) written, nothing else.  Larger segments, and the flat form, are grouped by the segmented chain
+ *   (the flat product chain) with generated positions as payload into the engine's buffers; then heads per 4096-key tile, the three
+ *   carries per segment over its tiles, and one scattered 4-byte store per key and output.
+ *   POINTERS AND LIMITS.  Everything is device memory.  THE ENGINE MUST HAVE has_payload = 1 AND n <= capacity: the positions travel
+ *   through the sort of large segments; the engine's buffers and result are overwritten (as after rsx_sort_from_to with outputs).
+ *   n <= 2^31, so MIN + MAX fits 32 bits; fewer than 2^32 - 1 segments.  n == 0, or no segments with offsets given, return RSX_OK and
+ *   launch nothing.  Keys 16-byte aligned, outputs 4-byte, offsets 8-byte.  Scratch grows on demand, never inside a capture (run one call
+ *   of the shape first).  Asynchronous on the engine's stream, nothing read back, capturable, every launch sized from n and num_segments
+ *   alone.  Offsets are validated on the device: with off[s+1] < off[s] or off[s+1] > n nothing is written and the next rsx_sync /
+ *   rsx_check_status reports RSX_CALCULATION_FAILED once, naming this call and the first such segment; the engine stays usable.
+ *   REFUSED AT ONCE: RSX_CALCULATION_FAILED for a null engine, flags != 0, method > RSX_RANK_AVERAGE, 2^32 - 1 segments or more,
+ *   n > 2^31; RSX_HOST_BUFFERS_FAILED for an engine without payload, n above the capacity, keys null or not 16-byte aligned, a null or
+ *   misaligned d_rank_out, a misaligned d_ties_out or d_offsets, an output overlapping an input or the other output, anything
+ *   overlapping the engine's buffers. */
+#define RSX_RANK_ORDINAL 0   /* position in the segment's stable sort: ties in index order */
+#define RSX_RANK_MIN     1   /* number of keys strictly before it ("competition" rank) */
+#define RSX_RANK_MAX     2   /* min + (size of its tie group) - 1 */
+#define RSX_RANK_DENSE   3   /* number of DISTINCT keys strictly before it */
+#define RSX_RANK_AVERAGE 4   /* min + max: TWICE the average rank, so it stays an exact integer */
+int rsx_segmented_rank(rsx_engine* e, const void* d_keys, uint64_t n, const uint64_t* d_offsets /* or NULL: one segment [0, n) */,
+                       uint64_t num_segments, uint32_t flags /* must be 0 */, uint32_t method, uint32_t* d_rank_out, uint32_t* d_ties_out /* or NULL */);
 /* rsx_segmented_reduce: SUM, MIN, MAX, ARGMIN or ARGMAX of the values of every segment (cub::DeviceSegmentedReduce; torch.segment_reduce;
  *   x.sum(-1), amax, argmax over the rows of a batch).  Nothing is sorted and there are no keys: the engine's key kind does not matter.
  *   RESULT.  d_values_out[s] = op over v[off[s] .. off[s+1]) for EVERY s < S: dense by segment id, not packed.  d_offsets == NULL is the

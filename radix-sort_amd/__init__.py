@@ -51,6 +51,8 @@ WEIGHT_UINT32, WEIGHT_FLOAT32, WEIGHT_FLOAT64 = 0, 1, 2                        #
 WHIST_SIGNED = 256         # RSX_WHIST_SIGNED: flags bit 8 of rsx_segmented_weighted_histogram
 SET_INTERSECTION, SET_DIFFERENCE, SET_UNION, SET_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3       # RSX_SET_*: op of rsx_segmented_set_op
 JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = 0, 1, 2, 3                                 # RSX_JOIN_*: op of rsx_segmented_join
+RANK_ORDINAL, RANK_MIN, RANK_MAX, RANK_DENSE, RANK_AVERAGE = 0, 1, 2, 3, 4               # RSX_RANK_*: method of rsx_segmented_rank
+RANK_METHODS = {"ordinal": RANK_ORDINAL, "min": RANK_MIN, "max": RANK_MAX, "dense": RANK_DENSE, "average": RANK_AVERAGE}
 # rsx_experimental_option (include/radixsort_hip_experiments.h): known to the EXPERIMENTS build only (experiments()); the product library refuses them
 XOPT_DEBUG_RAISE_SCAN_TIMEOUT, XOPT_INLINE_SCAN, XOPT_INLINE_SCAN_MAX_GROUPS, XOPT_REORDER8_KERNEL, XOPT_REORDER8_STAY = 16, 17, 18, 19, 20
 EXPERIMENTS_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tools", "_variants", "libradixsort_hip_experiments.so")
@@ -61,7 +63,7 @@ SYMBOLS = [
     "rsx_create", "rsx_destroy", "rsx_set_stream", "rsx_get_stream", "rsx_set_option", "rsx_get_geometry", "rsx_resize",
     "rsx_upload", "rsx_fill_pad", "rsx_download", "rsx_pin_host", "rsx_unpin_host", "rsx_pipeline_submit", "rsx_pipeline_wait", "rsx_host_device_pointer",
     "rsx_histogram", "rsx_scan", "rsx_paste", "rsx_reorder", "rsx_sort", "rsx_sync", "rsx_check_status",
-    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_weighted_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_segmented_merge", "rsx_segmented_set_op", "rsx_segmented_histogram", "rsx_segmented_weighted_histogram", "rsx_segmented_sample", "rsx_segmented_reduce", "rsx_segmented_expand", "rsx_segmented_join", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
+    "rsx_sort_from", "rsx_partition", "rsx_partition_count", "rsx_partition_scatter", "rsx_sample_keys", "rsx_partition_count_split", "rsx_partition_scatter_split", "rsx_peer_alloc", "rsx_peer_free", "rsx_peer_open", "rsx_peer_close", "rsx_peer_enable", "rsx_sort_from_to", "rsx_segmented_sort", "rsx_segmented_topk", "rsx_segmented_select", "rsx_segmented_weighted_select", "rsx_segmented_unique", "rsx_segmented_reduce_by_key", "rsx_segmented_scan", "rsx_segmented_search", "rsx_segmented_compact", "rsx_segmented_merge", "rsx_segmented_set_op", "rsx_segmented_histogram", "rsx_segmented_weighted_histogram", "rsx_segmented_sample", "rsx_segmented_rank", "rsx_segmented_reduce", "rsx_segmented_expand", "rsx_segmented_join", "rsx_msd_count", "rsx_msd_scatter", "rsx_msd_plan", "rsx_msd_plan_wait", "rsx_msd_push", "rsx_copy_to_device", "rsx_copy_from_device", "rsx_copy_on_device", "rsx_wait_for", "rsx_record_mark", "rsx_wait_mark", "rsx_key_range", "rsx_partition_range", "rsx_result_device", "rsx_copy_result", "rsx_tile_map", "rsx_timings",
 ]
 
 
@@ -180,6 +182,7 @@ def load_library() -> C.CDLL:
         "rsx_segmented_histogram": ([P, P, U64, P, U64, P, U64, U64, C.c_uint32, U64, C.c_uint32, P], I),
         "rsx_segmented_weighted_histogram": ([P, P, P, U64, P, U64, P, U64, U64, C.c_uint32, U64, C.c_uint32, C.c_uint32, C.c_int32, P], I),
         "rsx_segmented_sample": ([P, P, P, U64, P, U64, P, P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, P, P, P], I),
+        "rsx_segmented_rank": ([P, P, U64, P, U64, C.c_uint32, C.c_uint32, P, P], I),
         "rsx_segmented_reduce": ([P, P, U64, P, U64, C.c_uint32, C.c_uint32, C.c_uint32, P, P], I),
         "rsx_segmented_expand": ([P, P, U64, C.c_uint32, P, U64, U64, P, C.c_uint32, P, P, P], I),
         "rsx_segmented_join": ([P, P, U64, P, P, U64, P, U64, C.c_uint32, C.c_uint32, U64, P, P, P, P], I),
@@ -706,6 +709,17 @@ class Engine:
         self._check(self.lib.rsx_segmented_sample(
             self._h, _opt(d_keys), _opt(d_weights), n, _opt(d_offsets), num_segments, _opt(d_bounds), _opt(d_targets), draws_per_segment, flags,
             weight_kind, weight_exp, _opt(d_index_out), _opt(d_mass_out), _opt(d_total_out)), "rsx_segmented_sample")
+
+    def segmented_rank(self, d_keys: int, n: int, d_offsets: int | None, num_segments: int, method: int, d_rank_out: int,
+                       d_ties_out: int | None = None) -> None:
+        """The 0-based rank (uint32) of every key inside its segment [off[s], off[s+1]) in the engine's order, under the tie rule `method`
+        (RANK_ORDINAL: the position in the stable sort; RANK_MIN / RANK_MAX: the first / last position of its tie group; RANK_DENSE: the
+        distinct keys before it; RANK_AVERAGE: min + max, TWICE the average rank), and to d_ties_out (optional) the size of its tie group.
+        Keys tie iff their bits are equal (floats: IEEE 754 totalOrder).  d_offsets None: ONE segment [0, n).  Needs a payload engine and
+        n <= capacity; the engine's buffers are overwritten.  No atomic and no float operation: bitwise reproducible.  Asynchronous on the
+        engine's stream; bad offsets (nothing is written then) are reported by the next sync() / check_status()."""
+        self._check(self.lib.rsx_segmented_rank(self._h, _opt(d_keys), n, _opt(d_offsets), num_segments, 0, method, _opt(d_rank_out), _opt(d_ties_out)),
+                    "rsx_segmented_rank")
 
     # -- exchange step of the sharded sort on the top B <= 8 bits ----------------
     def msd_count(self, d_keys: int, n: int, bits: int, world: int, d_counts: int) -> None:
@@ -2679,6 +2693,91 @@ def sample_rows(probs, u=None, top_k=None, top_p=None, min_p=None, generator=Non
     else:
         idx, _, _ = segmented_sample(flat, offsets, u=uu.reshape(rows), bound=bound.to(probs.dtype).reshape(rows), descending=True)
     return idx.reshape(lead)
+
+
+# -- ranks on torch tensors -------------------------------------------------------------------------------------------------------------
+def _rank_check(what: str, x, method) -> int:
+    """The method's code and the rules of the input that need no device: an unknown method and a host tensor raise ValueError, a dtype
+    that is no key type (bfloat16, float16, bool, ...) TypeError."""
+    code = RANK_METHODS.get(method) if isinstance(method, str) else None
+    if code is None:
+        raise ValueError(f"{what}: method must be one of {', '.join(RANK_METHODS)}, not {method!r}")
+    _args.key_name(what, x)
+    if not x.is_cuda:
+        raise ValueError(f"{what}: the input must be a device tensor (there is no CPU path)")
+    return code
+
+
+def _rank_call(what: str, keys, offsets, nseg: int, code: int, descending: bool, want_ties: bool):
+    """One rsx_segmented_rank call on a 1-D device tensor (offsets None: one segment).  Returns (ranks, ties) as int32 tensors holding the
+    uint32 results (below 2^32: min + max of 2^31 keys), zero outside the segments; nothing is read back."""
+    import torch
+    n = keys.numel()
+    _args.check_count(what, "rsx_segmented_rank", "elements", n)
+    ranks = torch.zeros(n, dtype=torch.int32, device=keys.device)
+    ties = torch.zeros(n, dtype=torch.int32, device=keys.device) if want_ties else None
+    if n > 0 and nseg > 0:
+        k_in = _aligned_copy(keys)
+        off = _args.as_offsets(offsets)
+        eng = _segmented_engine(*_args.device_and_stream(keys), _args.dtype_name(keys), True, bool(descending), n)
+        eng.segmented_rank(k_in.data_ptr(), n, _args.ptr(off), nseg, code, ranks.data_ptr(), _args.ptr(ties))
+        eng.check_status()      # reports bad offsets of calls that have already finished
+    return ranks, ties
+
+
+def _rank_result(ranks, code: int):
+    """int64 ranks; float64 (min + max) / 2 for the average"""
+    import torch
+    wide = _args.widen(ranks)
+    return wide.to(torch.float64) / 2 if code == RANK_AVERAGE else wide
+
+
+def segmented_rank(keys, offsets, method: str = "average", descending: bool = False, return_ties: bool = False):
+    """The 0-based rank of every key inside its segment [offsets[s], offsets[s+1]) of the 1-D device tensor `keys` in ONE engine call
+    (rsx_segmented_rank).  method: "ordinal" (the position in the segment's stable sort), "min", "max" (the first / last position of the
+    key's tie group), "dense" (the distinct keys before it) or "average" ((min + max) / 2).  Returns ranks shaped like keys, int64, for
+    "average" float64; with return_ties also the int64 size of every key's tie group.  Entries outside [offsets[0], offsets[-1]) are 0.
+    descending=True ranks the largest key 0.  Keys tie iff their bits are equal: float keys follow IEEE 754 totalOrder, so -0.0 ranks
+    below +0.0 and NaNs rank by sign and payload.  Bad offsets raise at the engine's next synchronisation (this call does not read
+    them); nothing is written then."""
+    code = _rank_check("segmented_rank", keys, method)
+    if keys.dim() != 1:
+        raise ValueError("segmented_rank: keys must be a 1-D device tensor")
+    _args.check_offsets("segmented_rank", offsets, keys.device)
+    ranks, ties = _rank_call("segmented_rank", keys, offsets, max(offsets.numel() - 1, 0), code, descending, return_ties)
+    out = _rank_result(ranks, code)
+    return (out, _args.widen(ties)) if return_ties else out
+
+
+def rankdata(x, method: str = "average", dim=-1, descending: bool = False, pct: bool = False):
+    """scipy.stats.rankdata(x, method, axis=dim) on a device tensor: 1-based ranks shaped like x, float64 for "average" and int64
+    otherwise; the rows along `dim` are the segments of ONE rsx_segmented_rank call, dim=None ranks the flattened tensor (the flat sort
+    chain).  pct=True divides by the row length (float64), as pandas' rank(pct=True).  descending=True ranks the largest entry first.
+    Equal to scipy for integers and for floats without -0.0 and NaN.  Differences: keys tie iff their bits are equal and float keys
+    follow IEEE 754 totalOrder, so -0.0 ranks below +0.0 (scipy ties them), and NaNs rank by sign and payload, equal-bit NaNs tying
+    (scipy's default propagates NaN to the whole row).  Supported dtypes: int32, uint32, int64, uint64, float32, float64."""
+    import torch
+    code = _rank_check("rankdata", x, method)
+    if dim is None:
+        flat = x.reshape(-1)
+        size = flat.numel()
+        ranks, _ = _rank_call("rankdata", flat, None, 1, code, descending, False)
+        out = _rank_result(ranks, code).reshape(x.shape) + 1
+    else:
+        if x.dim() == 0:
+            raise ValueError("rankdata: a 0-d tensor has no dimension to rank along (dim=None ranks it flattened)")
+        dim = dim % x.dim()
+        size = x.shape[dim]
+        xm = x.movedim(dim, -1)
+        rows = xm.numel() // size if size else 0
+        flat = xm.contiguous().reshape(-1)
+        offsets = torch.arange(0, rows + 1, device=x.device, dtype=torch.int64) * size
+        ranks, _ = _rank_call("rankdata", flat, offsets, rows, code, descending, False)
+        out = (_rank_result(ranks, code) + 1).reshape(xm.shape).movedim(-1, dim)
+    if pct:
+        # (by a device scalar: a true IEEE division; torch multiplies by the reciprocal of a host scalar, which is not the same number)
+        out = out.to(torch.float64) / torch.full((), float(max(size, 1)), dtype=torch.float64, device=x.device)
+    return out
 
 
 # -- merge on torch tensors -------------------------------------------------------------------------------------------------------------

@@ -7,7 +7,7 @@ namespace {
 
 template <typename Key>
 int segmented_enqueue(rsx_engine* e, const Key* kin, const uint32_t* pin, uint64_t n, const uint64_t* off, uint64_t nseg, Key* kout,
-                      uint32_t* pout, bool carry_payload = true)
+                      uint32_t* pout, bool carry_payload = true, bool small_segments = true)
 {
     const SegShape s = seg_shape(n, nseg);
     int rc = ensure_segmented(e, s, nseg);
@@ -28,12 +28,19 @@ int segmented_enqueue(rsx_engine* e, const Key* kin, const uint32_t* pin, uint64
                        off, nseg, n, e->seg_bsum, e->seg_hdr, e->seg_list, e->seg_large, e->seg_tstart, kin, kout, pin, pout);
     hipLaunchKernelGGL(rsx::seg_scan_kernel, dim3(1), dim3(rsx::kSegScanThreads), 0, e->stream, e->seg_bsum, static_cast<uint32_t>(s.nblocks), e->seg_hdr,
                        e->seg_tstart, n, s.max_large, s.max_tiles, e->seg_status);
-    hipLaunchKernelGGL((rsx::seg_classify_kernel<Key, true>), dim3(static_cast<uint32_t>(s.nblocks)), dim3(rsx::kSegClassifyThreads), 0, e->stream,
-                       off, nseg, n, e->seg_bsum, e->seg_hdr, e->seg_list, e->seg_large, e->seg_tstart, kin, kout, pin, pout);
+    // (small_segments = false, rsx_segmented_rank: the caller ranks the segments of at most one tile itself, from the list; the chain alone
+    // runs here, and the top-k's writing classify, which copies no one-key segment)
+    if (small_segments) {
+        hipLaunchKernelGGL((rsx::seg_classify_kernel<Key, true>), dim3(static_cast<uint32_t>(s.nblocks)), dim3(rsx::kSegClassifyThreads), 0, e->stream,
+                           off, nseg, n, e->seg_bsum, e->seg_hdr, e->seg_list, e->seg_large, e->seg_tstart, kin, kout, pin, pout);
+    } else {
+        hipLaunchKernelGGL((rsx::seg_classify_kernel<Key, true, true>), dim3(static_cast<uint32_t>(s.nblocks)), dim3(rsx::kSegClassifyThreads), 0, e->stream,
+                           off, nseg, n, e->seg_bsum, e->seg_hdr, e->seg_list, e->seg_large, e->seg_tstart, kin, kout, pin, pout);
+    }
     RSX_TRY(hipGetLastError(), RSX_CALCULATION_FAILED);
 
     // 2. small segments: one workgroup per segment, all passes in LDS; grids bounded by what could exist and by residency
-    for_each_small_class(nseg, n, cus, [&](int c, uint64_t grid, auto shape) {
+    if (small_segments) for_each_small_class(nseg, n, cus, [&](int c, uint64_t grid, auto shape) {
         constexpr int T = decltype(shape)::THREADS, K = decltype(shape)::KPT;
         constexpr size_t lds = rsx::SegSortLayout<Key, T, K>::BYTES;
         if (payload) {

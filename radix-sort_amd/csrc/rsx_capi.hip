@@ -28,6 +28,7 @@
 #include "rsx_bins.hpp"
 #include "rsx_wbins.hpp"
 #include "rsx_sample.hpp"
+#include "rsx_rank.hpp"
 #include "rsx_args.hpp"
 
 #include <hip/hip_runtime.h>
@@ -1290,6 +1291,7 @@ constexpr uint32_t kStatusCallJoin = 6;
 constexpr uint32_t kStatusCallWselect = 7;
 constexpr uint32_t kStatusCallWhistogram = 8;
 constexpr uint32_t kStatusCallSample = 9;
+constexpr uint32_t kStatusCallRank = 10;
 int check_scan_timeout(rsx_engine* e, int status)
 {
     if (e->seg_status_host) {
@@ -1328,6 +1330,9 @@ int check_scan_timeout(rsx_engine* e, int status)
                                      "usable)").c_str());
             if (call == kStatusCallSample)
                 return fail(status, ("rsx_segmented_sample: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; nothing was written (the "
+                                     "first such segment of the call; reported once; the engine remains usable)").c_str());
+            if (call == kStatusCallRank)
+                return fail(status, ("rsx_segmented_rank: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; nothing was written (the "
                                      "first such segment of the call; reported once; the engine remains usable)").c_str());
             if (call == kStatusCallWhistogram)
                 return fail(status, ("rsx_segmented_weighted_histogram: segment " + std::to_string(v - 1) + " has off[s+1] < off[s] or off[s+1] > n; every sum of "
@@ -2458,6 +2463,7 @@ int rsx_peer_enable(rsx_engine* e, int peer_device)
 #include "capi_select.inc"
 #include "capi_wselect.inc"
 #include "capi_unique.inc"
+#include "capi_rank.inc"
 #include "capi_reduce.inc"
 #include "capi_scan.inc"
 #include "capi_search.inc"
