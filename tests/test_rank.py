@@ -1,7 +1,9 @@
 """CPU tests of the segmented rank (rsx_segmented_rank; tests/test_gpu_rank.py holds the GPU ones): the header, the binding and the exports
 agree; the referee tests/_rank_ref.py by hand for all five methods and against scipy.stats.rankdata where scipy is installed; the carries
 over a sorted segment's tiles and the rank rule — csrc/rsx_rank_math.hpp through the stand-alone rank_selftest, plain and under
--fsanitize=address,undefined — against the referee; and the argument errors of the torch helpers that need no device."""
+-fsanitize=address,undefined — against the referee; the argument errors of the torch helpers that need no device; the one-lexsort form of
+the referee against the looped one; and every layout of tests/test_gpu_rank_paths.py pinned to the launch path it is named for, at three
+CU counts where the path depends on the count."""
 import ctypes as C
 import os
 import re
@@ -11,6 +13,7 @@ import numpy as np
 import pytest
 
 import _rank_ref as R
+import _segmented_ref as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "radix-sort_amd", "host", "bin")
@@ -159,3 +162,174 @@ def test_helper_argument_errors(rsx):
             rsx.rankdata(torch.zeros(4, dtype=dtype))
         with pytest.raises(TypeError, match="unsupported key type"):
             rsx.segmented_rank(torch.zeros(4, dtype=dtype), off)
+
+
+# -- the referee in one lexsort; the layouts of tests/test_gpu_rank_paths.py reach their paths ----------------------------------------------------
+
+CU_COUNTS = [256, 304, 128]                                                     # those of tests/test_sample.py
+MIXED_LENGTHS = [0, 1, 2, 260, 0, 1200, 3500, 30000, 1, 4097, 700, 9000, 4096, 0]      # tests/test_gpu_rank.py's, from 37 with a tail of 50
+
+
+def _same(many, looped):
+    return all(a.dtype == b.dtype and a.tobytes() == b.tobytes() for a, b in zip(many, looped))
+
+
+@pytest.mark.parametrize("descending", [False, True])
+def test_oracle_many_equals_the_looped_oracle_on_the_mixed_layout(descending):
+    rng = np.random.default_rng(40 + descending)
+    off = S.offsets_from(MIXED_LENGTHS, start=37)
+    n = int(off[-1]) + 50
+    for dt in (np.uint32, np.float64, np.int64):
+        x = (rng.standard_normal(n) * 2).round().astype(dt) if np.dtype(dt).kind == "f" else rng.integers(0, 9, n).astype(dt)
+        assert _same(R.rank_oracle_many(x, off, descending, fill=0xC3C3C3C3), R.rank_oracle(x, off, descending, fill=0xC3C3C3C3)), np.dtype(dt).name
+
+
+def test_oracle_many_equals_the_looped_oracle_on_many_tiny_segments():
+    rng = np.random.default_rng(42)
+    off = S.offsets_from(rng.integers(0, 4, 5000), start=2)
+    n = int(off[-1]) + 3
+    x = rng.integers(-2, 2, n).astype(np.int32)
+    many, looped = R.rank_oracle_many(x, off, fill=5), R.rank_oracle(x, off, fill=5)
+    assert _same(many, looped) and not many[2][:2].any() and not many[2][-3:].any() and many[2][2:-3].all()
+    none = R.rank_oracle_many(x, np.array([4, 4, 4], dtype=np.uint64), fill=5)                        # nothing inside any segment
+    assert not none[2].any() and np.all(none[0] == 5) and np.all(none[1] == 5)
+
+
+def test_rank_geometry_by_hand():
+    # 3 segments at 256 CUs: a one-key, a class-0 and a large one of 3 tiles (it begins at 4090 and ends at 4090 + 4200 = 8290 > 8192)
+    off = np.array([4000, 4001, 4090, 8290], dtype=np.uint64)
+    g = R.rank_geometry(off, 9000, 256)
+    assert (g["ones"], g["count"], g["nlarge"], g["tiles"]) == (1, [1, 0, 0], 1, 3) and (g["max_large"], g["max_tiles"]) == (2, 5)
+    assert (g["ones_grid"], g["ones_trips"], g["small_trips"], g["tile_grid"], g["tile_trips"], g["join_grid"], g["join_trips"]) == (1, 1, [1, 0, 0], 5, 1, 2, 1)
+    assert (g["T"], g["join_per"], g["join_used"]) == ([3], [1], [3])
+    flat = R.rank_geometry(None, 257 * R.TILE - 100, 256)
+    assert (flat["nlarge"], flat["tiles"], flat["T"], flat["join_per"], flat["join_used"]) == (1, 257, [257], [2], [129])
+    assert (flat["ones_trips"], flat["small_trips"], flat["tile_grid"], flat["tile_trips"], flat["join_grid"], flat["join_trips"]) == (0, [0, 0, 0], 257, 1, 1, 1)
+    assert R.rank_geometry(None, 5000, 256)["T"] == [2] and R.rank_geometry(None, 5, 256)["T"] == [1]
+
+
+def test_join_facts_by_hand():
+    # a segment from global index 4094: tiles of 2, 4096 and 3 keys.  Sorted keys: 5 | 5 ... 5 7 | 7 8 8
+    s = np.concatenate([[5, 5], np.full(4095, 5), [7], [7, 8, 8]]).astype(np.uint32)
+    f = R.join_facts(4094, s)
+    assert f["edges"] == [(1, 0, 0), (1, 4097, 4097), (1, 4099, 4099)] and (f["T"], f["per"], f["used"], f["idle"]) == (3, 1, 3, 253)
+    assert f["last_key_head"] and not f["first_key_head"] and not f["wave_headless"] and f["thread_headless"] == [False] * 3
+    s = np.concatenate([[5, 6], np.full(4096, 7), [8, 8, 8]]).astype(np.uint32)             # the run of 7 fills tile 1 exactly
+    f = R.join_facts(4094, s)
+    assert f["edges"] == [(2, 0, 1), (1, 2, 2), (1, 4098, 4098)] and f["first_key_head"] and f["last_key_head"] and f["all_heads_tiles"] == 1
+    s = np.zeros(3 * R.TILE, dtype=np.uint64)                                    # one run over three whole tiles
+    f = R.join_facts(0, s)
+    assert f["edges"] == [(1, 0, 0), (0, None, None), (0, None, None)] and f["thread_headless"] == [False, True, True]
+    assert R.tile_facts(0, s) == (True, True)
+
+
+@pytest.mark.parametrize("cus", CU_COUNTS)
+def test_stride_layouts_give_the_small_kernel_a_second_trip(cus):
+    for cls in range(3):
+        n, off = S.stride_layout(cls, cus)
+        g = R.rank_geometry(off, n, cus)
+        assert g["small_trips"][cls] == 2 and g["count"][cls] > g["grid"][cls] == cus * S.PER_CU[cls] and g["nlarge"] == 0
+        lens = np.diff(off.astype(np.int64))
+        order, grid = g["lists"][cls], g["grid"][cls]
+        second = np.arange(grid, g["count"][cls])
+        assert np.all(lens[order[second]] < lens[order[second - grid]])          # the second item runs over a longer segment's image
+
+
+def test_pad_equal_layout_and_keys():
+    n, off, planted = R.pad_equal_layout()
+    g = R.rank_geometry(off, n, 256)
+    lens = np.diff(off.astype(np.int64))
+    assert g["count"] == [3, 3, 3] and g["ones"] == 3 and g["nlarge"] == 1 and lens[g["large"][0]] == 4097 + 300 and len(planted) == 10
+    for c, tile in enumerate(R.CLASS_TILE):
+        assert sorted(lens[g["lists"][c]].tolist()) == sorted([tile - 1, tile - 17, 2 * tile // 3]) and max(lens[g["lists"][c]]) < tile
+    assert [R.pad_value(dt, d).view(np.uint32).item() for dt, d in R.PAD_PAIRS] == [0xFFFFFFFF, 0, 0x7FFFFFFF, 0xFFFFFFFF]
+    for i, (dt, descending) in enumerate(R.PAD_PAIRS):
+        x, counts = R.pad_equal_keys(dt, descending, n, off, planted, np.random.default_rng(i))
+        pad = R.pad_value(dt, descending).view(np.uint32)
+        ranks, ties, _ = R.rank_oracle(x, off, descending)
+        for s in planted:
+            a, b = int(off[s]), int(off[s + 1])
+            at = np.flatnonzero(x[a:b].view(np.uint32) == pad)
+            assert len(at) == counts[s] == (b - a) // 3 + 5 and np.all(at[-((b - a) // 3):] == np.arange(b - (b - a) // 3, b) - a)
+            assert np.all(ties[a:b][at] == counts[s]) and np.all(ranks[R.MAX][a:b][at] == b - a - 1) and np.all(ranks[R.MIN][a:b][at] == b - a - counts[s])
+            assert int(ranks[R.DENSE][a:b].max()) == int(ranks[R.DENSE][a:b][at[0]]) >= 2          # the last run of the segment, behind others
+
+
+@pytest.mark.parametrize("cus", CU_COUNTS)
+def test_sparse_large_reaches_the_ones_second_trip(cus):
+    n, off = S.sparse_large()
+    g = R.rank_geometry(off, n, cus)
+    assert g["ones_trips"] >= 2 and g["per"] == 2 and g["small_trips"][0] >= 2 and g["nlarge"] >= 30 and g["large_blocks"] >= 30
+    assert g["ones"] > 100000 and g["ones_grid"] == cus * 4
+    if cus == 256:
+        assert (g["ones_trips"], g["small_trips"][0], g["nlarge"], g["large_blocks"]) == (3, 37, 43, 41)
+    nb, bad = S.sparse_large_bad()
+    assert nb == n and R.rank_geometry(bad, n, cus)["first_bad"] == 550001
+
+
+def test_join_layout_reaches_every_path_of_the_join():
+    n, off, names, runs = R.join_layout()
+    g = R.rank_geometry(off, n, 256)
+    o = off.astype(np.int64)
+    assert g["T"] == list(R.JOIN_TILES) == [65, 256, 385] and g["join_per"] == [1, 1, 2] and g["join_used"] == [65, 256, 193]
+    assert all(o[s] % R.TILE for s in names.values()) and g["large"].tolist() == list(names.values()) and g["count"][1] and g["count"][2] and g["ones"]
+    for dt, descending in (("uint32", False), ("float64", True)):
+        x = R.join_keys(dt, descending, n, off, names, runs, np.random.default_rng(3))
+        facts = [R.join_facts(a, s) for a, s in R.sorted_keys_layout(x, off, descending)]
+        t65, t256, t385 = facts
+        paths = R.join_paths(facts)
+        assert all(paths.values()), [name for name, reached in paths.items() if not reached]
+        assert (t65["used"], t65["idle"]) == (65, 191) and not t65["thread_headless"][64] and any(t65["thread_headless"])      # one record in the second wave
+        assert (t256["per"], t256["used"], t256["idle"]) == (1, 256, 0) and t256["wave_headless"] and all(t256["thread_headless"][61:195])
+        assert not t256["thread_headless"][60] and not t256["thread_headless"][195]
+        assert (t385["per"], t385["used"], t385["idle"], t385["last_thread_tiles"]) == (2, 193, 63, 1)
+        assert t385["thread_headless"][7] and t385["thread_headless"][8] and not t385["thread_headless"][6] and not t385["thread_headless"][9]
+        assert t385["first_key_head"] and t385["last_key_head"] and t385["all_heads_tiles"] >= 8 and t385["wave_headless"]
+        assert all(t385["thread_headless"][51:192]) and not t385["thread_headless"][50] and not t385["thread_headless"][192]
+        e = t385["edges"]
+        assert e[12][0] == 1 and all(t[0] == 0 for t in e[13:18]) and e[11][2] == e[12][1] - 1     # the 6-tile run begins with tile 12, behind a one-key run ...
+        assert e[18][1] == e[12][1] + 6 * R.TILE and e[19][2] == e[18][1] + 2 * R.TILE - 1          # ... and ends with tile 17; a run from tile 19's last key
+
+
+@pytest.mark.parametrize("cus", CU_COUNTS)
+def test_grid_stride_layout_reaches_the_second_trips(cus):
+    n, off = R.grid_stride_layout(cus)
+    g = R.rank_geometry(off, n, cus)
+    lens = np.diff(off.astype(np.int64))
+    assert g["nlarge"] == cus * 8 + 40 and g["join_grid"] == g["tile_grid"] == cus * 8 and g["join_trips"] == 2 and g["tile_trips"] >= 2
+    assert 0 <= g["max_large"] - g["nlarge"] <= 3 and int(off[0]) == 5 and int(off[-1]) == n and g["ones"] >= 2 and (lens == 0).sum() >= 4
+    large = lens[g["large"]]
+    assert large.min() == R.TILE + 1 and R.TILE + 100 < large.max() <= R.TILE + 204 and set(g["T"]) <= {2, 3} and g["count"] == [0, 0, 0]
+
+
+def test_flat_sizes_cover_every_regime():
+    assert [R.flat_regime(n) for n in R.FLAT_SIZES] == ["small-tile self-scan", "self-scan", "self-scan", "self-scan", "look-ahead chain"]
+    assert R.flat_regime(4096) == "one tile" and R.flat_regime(5000) == "small-tile self-scan"
+    assert [R.flat_regime(n, 8) for n in R.FLAT_SIZES_8BIT] == ["8-bit chain"] * 2
+    assert max(R.FLAT_SIZES) <= R.FLAT_CAPACITY
+    per = [R.rank_geometry(None, n, 256)["join_per"][0] for n in R.FLAT_SIZES]
+    assert per == [1, 1, 2, 4, 5] and R.rank_geometry(None, R.FLAT_SIZES[2], 256)["join_used"] == [129]
+    # tests/test_gpu_rank.py's flat form stops at 10 000 keys: one tile and the small-tile self-scan only
+    assert {R.flat_regime(n) for n in (1, 5, 4096, 4097, 10000)} == {"one tile", "small-tile self-scan"}
+
+
+def test_replay_layouts_keep_the_size_and_change_the_classes():
+    n = sum(MIXED_LENGTHS) + 37 + 50
+    base = R.rank_geometry(S.offsets_from(MIXED_LENGTHS, start=37), n, 256)
+    assert base["count"] == [1, 2, 3] and base["nlarge"] == 3 and base["ones"] == 2
+    seen = {}
+    for name, lengths in R.REPLAY_LENGTHS.items():
+        off = S.offsets_from(lengths, start=R.REPLAY_STARTS[name])
+        assert len(lengths) == len(MIXED_LENGTHS) and int(off[-1]) <= n
+        g = R.rank_geometry(off, n, 256)
+        assert g["chain_ok"] == 1 and g["nlarge"] <= g["max_large"] == base["max_large"]
+        seen[name] = (g["count"], g["nlarge"], g["ones"])
+    assert seen["another class mix"] == ([3, 2, 3], 3, 2) and seen["no large segment"] == ([3, 2, 7], 0, 1) and seen["large or empty"] == ([0, 0, 0], 6, 0)
+
+
+def test_first_suite_stays_on_the_first_trips():
+    """what tests/test_gpu_rank.py's largest call reaches: one trip everywhere, join records in the first eight threads of one wave"""
+    off = S.offsets_from(MIXED_LENGTHS, start=37)
+    g = R.rank_geometry(off, sum(MIXED_LENGTHS) + 87, 256)
+    assert g["ones_trips"] == 1 and max(g["small_trips"]) == 1 and g["tile_trips"] == 1 and g["join_trips"] == 1 and g["per"] == 1
+    assert max(g["T"]) <= 9 and max(g["join_per"]) == 1
